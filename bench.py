@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: end-to-end frame-pairs/s (V2ce3d UNet + LDATI) at 346x260.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload e2e|pano|ldati_stress|ldati_sparse|voxelize]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload e2e|pano|ldati_stress|ldati_sparse|voxelize] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     (`python bench.py --gpus N` without torchrun starts the N ranks itself, as child processes)
 
@@ -60,6 +60,39 @@ def make_inputs(batch, first_seq, device):
     return torch.from_numpy(np.stack(xs)).to(device)
 
 
+DUMP_BYTES = 64 << 20               # --dump-outputs: at most this much in all
+DUMP_SEED = 20240611                # fixed seed of the sample --dump-outputs takes of a larger output
+
+
+def dump_sample(n, k):
+    """Sorted flat positions of a fixed, seeded sample of k out of n elements (all n when n <= k)."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write {name: array} as out_dir/<name>.npy; int64 and float64 as float64, everything else as float32."""
+    out = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        out[name] = a.astype(np.float64 if a.dtype in (np.int64, np.float64) else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BYTES, f"--dump-outputs: {total} bytes (limit {DUMP_BYTES})"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
+def dump_events(out_dir, ev):
+    """The arrays a caller of the timed path receives: the events of the step (ts, x, y, p, in record order) and the number of events of
+    every frame-pair.  More than 2^20 events are represented by a seeded sample; event_index.npy holds the sampled positions."""
+    idx = dump_sample(ev.num_events, 1 << 20)
+    sel = torch.from_numpy(idx).to(ev.device)
+    dump_outputs(out_dir, {"event_index": idx, "frame_counts": ev.frame_counts.astype(np.int64),
+                           **{k: getattr(ev, k)[sel] for k in ("ts", "x", "y", "p")}})
+
+
 def cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -113,20 +146,27 @@ def bench_voxelize(args, device, rank, world):
                ev.p[e - c:e].contiguous()) for e, c in zip(ends, ev.frame_counts)]
     n_events = int(ends[-1])
 
-    def step():
+    def step(keep=None):
         for f in frames:
-            gen_discretized_event_volume(f, (20, H, W))
+            v = gen_discretized_event_volume(f, (20, H, W))
+            if keep is not None:
+                keep.append(v)
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    last = [] if args.dump_outputs else None
     t0 = time.perf_counter()
     e0.record()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(last if i == args.steps - 1 else None)
     e1.record()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if last is not None and rank == 0:
+        vol = torch.stack(last).reshape(-1)                      # [24, 20, H, W] volumes, flattened
+        idx = dump_sample(vol.numel(), 4 << 20)
+        dump_outputs(args.dump_outputs, {"volume_index": idx, "volumes": vol[torch.from_numpy(idx).to(device)]})
     gpu_s = e0.elapsed_time(e1) * 1e-3
     nbytes = 13.0 * n_events + pairs * 20 * H * W * 4.0          # events read once + volumes written once
     achieved = nbytes * args.steps / gpu_s / 1e9
@@ -251,7 +291,12 @@ def main():
                          "profiles/r01_d_precision_report.json); f32 = exact f32 MFMA")
     ap.add_argument("--no-exact-f32", action="store_true", help="skip the extra exact-f32 measurement")
     ap.add_argument("--no-host-to-host", action="store_true", help="skip the host-to-host (PCIe-inclusive) measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0's outputs; "
+                         "f32/f64, at most 64 MB: a seeded sample of a larger output, its flat positions in <name>_index.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.batch is None:
         args.batch = 8 if args.workload == "pano" else 4
 
@@ -405,8 +450,9 @@ def main():
         return packed, ev
 
     status = [None]
+    last_events = [None]                                        # --dump-outputs: the events of the last timed step
 
-    def run_steps(k, profile):
+    def run_steps(k, profile, keep_last=False):
         pending = None
 
         def done(p):
@@ -414,6 +460,7 @@ def main():
             if ev._status is not None:                          # LDATI's device status word, folded on the stream
                 with torch.cuda.stream(side_stream) if side_stream is not None else contextlib.nullcontext():
                     status[0] = ev._status.clone() if status[0] is None else torch.maximum(status[0], ev._status)
+            return ev
         nonlocal gather, gather_aux
         t_x = time.perf_counter()
         gather, gather_aux = new_exchange()
@@ -424,7 +471,9 @@ def main():
                 done(pending)
             pending = nxt
         if pending is not None:
-            done(pending)
+            ev = done(pending)
+            if keep_last:
+                last_events[0] = ev
         t_loop = time.perf_counter() - t_x
         if gather is not None:
             gather.drain()                                      # the last step's exchange
@@ -462,12 +511,15 @@ def main():
         torch.distributed.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run_steps(args.steps, True)
+    run_steps(args.steps, True, keep_last=bool(args.dump_outputs))
     torch.cuda.synchronize()
     if dist_on:
         torch.distributed.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_events(args.dump_outputs, last_events[0])
+    last_events[0] = None
     # First-hardware-curve readiness: from eight ranks on the same steps are timed once more with the OTHER exchange,
     # so that the first run on an 8-GPU node shows north_star's RCCL gather ('device', the default and `value`) and the per-rank
     # PCIe download ('host') side by side.  V2CE_BENCH_BOTH_GATHERS=1 forces it at any world > 1, =0 switches it off.
