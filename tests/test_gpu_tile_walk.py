@@ -35,6 +35,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_ref import at as _at, conv_at, positions
+
 TOL = 1e-5
 N_CU = 256                         # MI355X
 SCALE_EXP = (-8, 0, 8)             # sequence b is 2^SCALE_EXP[b] times a unit-scale problem
@@ -219,49 +221,6 @@ def _inputs(c):
         I["wp"] = torch.randn(HEAD_CH, 32, generator=g) * 0.2
         I["bp"] = torch.randn(HEAD_CH, generator=g) * 0.1 * 2.0 ** SCALE_EXP[0]
     return I
-
-
-def _time_steps(T):
-    """First, last, and both members of a Winograd pair (all of them when T <= 4)."""
-    j = 2 * ((T // 2) // 2)
-    return sorted({0, T - 1, j, min(j + 1, T - 1)})
-
-
-def positions(B, T, Ho, Wo, seed, frac=0.12):
-    """Output positions (b, t, h, w) the reference evaluates: see the module docstring."""
-    sel = np.zeros((T, Ho, Wo), bool)
-    sel[_time_steps(T)] = True
-    sel[:, :2] = sel[:, -2:] = True
-    sel[:, :, :2] = sel[:, :, -2:] = True
-    rng = np.random.RandomState(seed)
-    out = []
-    for b in range(B):
-        m = sel | (rng.random_sample(sel.shape) < frac)
-        t, h, w = np.nonzero(m)
-        out.append((np.full_like(t, b), t, h, w))
-    return tuple(torch.from_numpy(np.concatenate(v)) for v in zip(*out))
-
-
-def conv_at(x, w, stride, pos, chunk=4096):
-    """f64 conv3d (padding k // 2, stride (1, s, s)) of x [B, C, T, H, W] with w [Cout, C, k, k, k] at the output
-    positions pos = (b, t, h, w): [N, Cout]."""
-    k = w.shape[2]
-    p = k // 2
-    xp = F.pad(x.double(), (p, p, p, p, p, p))
-    wm = w.double().reshape(w.shape[0], -1).t()
-    b, t, h, ww = pos
-    out = []
-    for i in range(0, b.numel(), chunk):
-        bi, ti, hi, wi = b[i:i + chunk], t[i:i + chunk], h[i:i + chunk] * stride, ww[i:i + chunk] * stride
-        cols = torch.stack([xp[bi, :, ti + dt, hi + dh, wi + dw] for dt in range(k) for dh in range(k) for dw in range(k)], dim=2)
-        out.append(cols.reshape(cols.shape[0], -1) @ wm)
-    return torch.cat(out)
-
-
-def _at(y, pos):
-    """[B, C, T, H, W] at the positions: [N, C]."""
-    b, t, h, w = pos
-    return y[b, :, t, h, w]
 
 
 def _upsample(x0, hw):
