@@ -928,16 +928,16 @@ __global__ __launch_bounds__(512) void wt_pack_kernel(WtBatch B) {   // (129 KB 
         G[1] = ((g0 + g1) + g2) * 0.5f;
         G[2] = ((g0 - g1) + g2) * 0.5f;
         G[3] = g2;
+        if (!PASS) {                                                  // max |g| over the three time taps (not over G: the bound is 1.5 max |g|)
+            m = fmaxf(m, fmaxf(fabsf(g0), fmaxf(fabsf(g1), fabsf(g2))));
+            continue;
+        }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            if (PASS) {
-                const float v = G[s] * w_scale;
-                const _Float16 h = (_Float16)v;
-                hi[(s * 9 + t9) * 514 + col * 16 + j] = h;
-                lo[(s * 9 + t9) * 514 + col * 16 + j] = (_Float16)(v - (float)h);
-            } else {
-                m = fmaxf(m, fabsf(s == 1 ? g1 : G[s]));              // max |g| over the three time taps (G[0] = g0, G[3] = g2)
-            }
+            const float v = G[s] * w_scale;
+            const _Float16 h = (_Float16)v;
+            hi[(s * 9 + t9) * 514 + col * 16 + j] = h;
+            lo[(s * 9 + t9) * 514 + col * 16 + j] = (_Float16)(v - (float)h);
         }
     }
     if (!PASS) {

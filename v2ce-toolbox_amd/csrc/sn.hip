@@ -410,6 +410,11 @@ extern "C" int v2ce_sn_update_batch(const v2ce_sn_layer *layers, int n, void *wo
     }
     V2CE_REQUIRE(n_iter == 0 || n_iter == n, V2CE_ERR_UNSUPPORTED,
                  "v2ce_sn_update_batch: pack-only layers (V2CE_SN_NO_ITERATE) go into a call of their own");
+    {                                                      // (checked before anything is enqueued: a refused call leaves u / v alone)
+        int n_up = 0;
+        for (int l = 0; l < n; ++l) n_up += (B.L[l].up_c0 && !B.L[l].no_pack) ? 1 : 0;
+        V2CE_REQUIRE(n_up <= 8, V2CE_ERR_UNSUPPORTED, "v2ce_sn_update_batch: at most eight layers with up_c0");
+    }
     hipStream_t st = as_stream(stream);
     if (n_iter) {
         hipLaunchKernelGGL(sn_batch_wt_u_kernel, dim3(B.col_blk[n], kRowChunks), dim3(256), 0, st, B);
@@ -428,11 +433,6 @@ extern "C" int v2ce_sn_update_batch(const v2ce_sn_layer *layers, int n, void *wo
             uf_rows[n_uf] = B.L[l].rows; uf_cin[n_uf] = B.L[l].cin; uf_c0[n_uf] = B.L[l].up_c0;
             ++n_uf;
         }
-    {
-        int n_up = 0;
-        for (int l = 0; l < n; ++l) n_up += (B.L[l].up_c0 && !B.L[l].no_pack) ? 1 : 0;
-        V2CE_REQUIRE(n_up <= 8, V2CE_ERR_UNSUPPORTED, "v2ce_sn_update_batch: at most eight layers with up_c0");
-    }
     if (n_uf) {
         const int rc = v2ce_up_fold_batch(uf_w, uf_rows, uf_cin, uf_c0, uf_sigma, uf_packed, n_uf, 0, st);
         if (rc != V2CE_OK) return rc;
