@@ -483,6 +483,34 @@ int v2ce_sampler_emit(const float *vox, int B, int H, int W, const v2ce_sampler_
                       int64_t *ts, int16_t *x, int16_t *y, int8_t *p, void *workspace, size_t workspace_bytes,
                       int32_t *status, v2ce_stream_t stream);
 
+/* Stage-2 score, csrc/tsdiff.hip: ts_diff_metric of train/scripts/stage2/stage2_metrics.py:22-88 for
+ * many frame pairs per call.  Events are SoA (timestamp int64 us, x, y int16, polarity int8); pair i owns GT events
+ * [gt_offsets[i], gt_offsets[i+1]) and predicted events [pred_offsets[i], pred_offsets[i+1]) (int64 [pairs+1],
+ * monotone, within [0, n_gt] / [0, n_pred]); fps [pairs] f64, finite and > 0.  GT polarity -1 counts as 0 (the
+ * caller's array is not modified); predicted polarity 0 is 0, any other value 1.  Per GT event:
+ *   d = min(1e6, min |t_pred - t_gt|) over the predicted events of its polarity in the cells
+ *       [max(x-r,0), min(x+r+1,W)) x [max(y-r,0), min(y+r+1,H)), the difference taken in int64;
+ *   cap = 1e6 / fps / 10 * 3 (f64, left to right); (double)d > cap: d = cap and the event overflows.
+ * pair_stats [pairs][3] int64 = {S, K, N}: S the exact sum of the uncapped d, K the overflow count, N the GT count.
+ * The reference's score is then avg = ((double)S + (double)K * cap) / N, overflow = K.  per_event_d [n_gt] f64 (may
+ * be NULL): each GT event's d.  status [1] (device int32) is zeroed here; a bit set on return means nothing was
+ * written to pair_stats / per_event_d: 1 offsets not monotone or out of range, 2 fps not finite or <= 0, 4 a GT x/y
+ * outside [0,W) x [0,H), 8 a GT polarity outside {-1, 0, 1}, 16 a predicted x/y outside the sensor.
+ * Workspace >= v2ce_tsdiff_workspace_bytes(pairs, H, W, n_pred), which returns 0 for pairs <= 0, H or W outside
+ * [1, 32767], 2*H*W >= 2^30 or n_pred outside [0, 2^31).  Pairs are processed in chunks whose cell table
+ * (chunk * 2 * H * W int32) stays near 46 MB; results do not depend on the chunking or the order of the events. */
+size_t v2ce_tsdiff_workspace_bytes(int pairs, int H, int W, int64_t n_pred);
+int v2ce_tsdiff(const int64_t *gt_ts, const int16_t *gt_x, const int16_t *gt_y, const int8_t *gt_p, const int64_t *gt_offsets,
+                int64_t n_gt, const int64_t *pred_ts, const int16_t *pred_x, const int16_t *pred_y, const int8_t *pred_p,
+                const int64_t *pred_offsets, int64_t n_pred, const double *fps, int pairs, int H, int W, int search_range,
+                double *per_event_d, int64_t *pair_stats, int32_t *status, void *workspace, size_t workspace_bytes,
+                v2ce_stream_t stream);
+#define V2CE_TSDIFF_BAD_OFFSETS 1
+#define V2CE_TSDIFF_BAD_FPS 2
+#define V2CE_TSDIFF_BAD_GT_XY 4
+#define V2CE_TSDIFF_BAD_GT_POLARITY 8
+#define V2CE_TSDIFF_BAD_PRED_XY 16
+
 /* One spectral-norm power iteration (spectral_norm.py:19-31), in place on u [rows], v [cols]:
  *   v = W^T u / (|W^T u| + 1e-12); u = W v / (|W v| + 1e-12); sigma = u . (W v)
  * w_bar [rows][cols] f32; sigma [1] f32 out; workspace >= v2ce_sn_workspace_bytes(rows, cols). */

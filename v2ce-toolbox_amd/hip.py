@@ -34,6 +34,7 @@ EXPORTS = [
     "v2ce_conv3d_fwd_up2", "v2ce_pack_weights_f16x2_up", "v2ce_pack_weights_f16x2_up_bytes", "v2ce_conv3d_up2_variant",
     "v2ce_conv3d_fwd_wt", "v2ce_conv3d_fwd_wt_tail", "v2ce_pack_weights_f16x2_wt", "v2ce_pack_weights_f16x2_wt_slice", "v2ce_conv3d_fwd_up2_part", "v2ce_pack_weights_f16x2_wt_bytes", "v2ce_conv3d_wt_variant",
     "v2ce_conv3d_head_f16x2", "v2ce_pack_head_weights_f16x2", "v2ce_pack_head_weights_f16x2_bytes", "v2ce_absmax_batch",
+    "v2ce_tsdiff_workspace_bytes", "v2ce_tsdiff",
 ]
 
 
@@ -204,6 +205,10 @@ def lib() -> ctypes.CDLL:
     L.v2ce_sampler_workspace_bytes.restype = sz
     L.v2ce_sampler_emit.argtypes = [vp, i32, i32, i32, so, i64, vp, vp, vp, vp, vp, sz, vp, vp]
     L.v2ce_sampler_emit.restype = ctypes.c_int
+    L.v2ce_tsdiff_workspace_bytes.argtypes = [i32, i32, i32, i64]
+    L.v2ce_tsdiff_workspace_bytes.restype = sz
+    L.v2ce_tsdiff.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
+    L.v2ce_tsdiff.restype = ctypes.c_int
     for name in ("v2ce_ldati_count", "v2ce_ldati_emit", "v2ce_events_pack",
                  "v2ce_conv3d_fwd", "v2ce_conv3d_variant", "v2ce_pack_weights", "v2ce_sn_power_iter"):
         getattr(L, name).restype = ctypes.c_int
