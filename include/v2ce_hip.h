@@ -435,8 +435,8 @@ int v2ce_pack_weights(const float *w, int Cout, int Cin, int k3, const float *si
 /* Voxeliser (the inverse of LDATI): gen_discretized_event_volume of
  * train/scripts/utils/events_utils.py:118-175.  SoA events on the device -> volume [2*bins][H][W]
  * f32 (zeroed here): time rescaled to [0, bins-1] over the set's own [t_min, t_max] (computed here
- * into t_range [2] int64, device), each event split between its floor and ceil bin, polarity 1 in
- * planes [0,bins), polarity 0 in [bins,2*bins).  Same f32 arithmetic as the reference per event;
+ * into t_range [2] int64, device), each event split between its floor and ceil bin, polarity > 0 in
+ * planes [0,bins), polarity <= 0 (0 or -1) in [bins,2*bins).  Same f32 arithmetic as the reference per event;
  * accumulation by float atomics (order differs).  n > 0 and t_max > t_min required (the reference
  * raises / produces NaN otherwise); events with x/y outside the volume are skipped (the reference
  * asserts). */
@@ -510,6 +510,56 @@ int v2ce_tsdiff(const int64_t *gt_ts, const int16_t *gt_x, const int16_t *gt_y, 
 #define V2CE_TSDIFF_BAD_GT_XY 4
 #define V2CE_TSDIFF_BAD_GT_POLARITY 8
 #define V2CE_TSDIFF_BAD_PRED_XY 16
+
+/* Stage-1 score (csrc/voxmetrics.hip): the metric classes of train/scripts/model/metrics.py (BinaryMatch,
+ * BinaryMatchF1, PoolMSE, MeanRatio) and nn.L1Loss for pred, gt [B][L][C][H][W] f32, contiguous, on the device.
+ * C must be 20 (channels (p c): 2 polarities x 10 bins); other channel counts are refused.  One record per sequence b
+ * (stats [B], device memory), sums that combine exactly across b:
+ *   op 0 raw (elementwise), 1 sum_c (the 10 bins of each polarity summed in order, f32), 2 sum_cp (the 20 channels
+ *   summed in order, f32): n = element count, tp / fp / fn of the binarised values (v > threshold, f32; NaN is never
+ *   above it);
+ *   abs_diff_sum = sum of f32 |p - g| in f64;  ratio_sum = sum of r = (p + 0.01f) / (g + 0.01f), r < 1 ? 1 / r : r;
+ *   per requested pool size k (pool_size[q] = pool_sizes[q], q < n_pools): pool_sq_sum = sum of the f32
+ *   (pool_k(p) - pool_k(g))^2 in f64 and pool_n the number of pooled values, where pool_k is AvgPool3d(k, stride k)
+ *   over ((l c), h, w) of each (b, polarity) (windows cross frame boundaries; each axis floored to a multiple of k;
+ *   a pooled value is the f32 sum of its k^3 values in (d, h, w) order / (float)(k^3)).
+ * k = 2 and 4 come with the fused pass over both tensors; every other k costs one extra launch.  Each k must lie in
+ * [1, min(10 L, H, W)] and n_pools in [0, V2CE_VOXMETRICS_MAX_POOLS].  No float atomics: the records are bit-identical
+ * run to run and do not depend on B.  stats_struct_size must be sizeof(v2ce_voxmetrics_stats) as the caller was built
+ * with; the library refuses any other value and writes its own size into every record's struct_size.
+ * Workspace >= v2ce_voxmetrics_workspace_bytes(...), which returns 0 for arguments the entry refuses. */
+#define V2CE_VOXMETRICS_MAX_POOLS 8
+typedef struct v2ce_voxmetrics_stats {
+    int64_t struct_size;
+    int64_t n[3], tp[3], fp[3], fn[3];
+    double abs_diff_sum, ratio_sum;
+    int64_t n_pools;
+    int64_t pool_size[V2CE_VOXMETRICS_MAX_POOLS];
+    int64_t pool_n[V2CE_VOXMETRICS_MAX_POOLS];
+    double pool_sq_sum[V2CE_VOXMETRICS_MAX_POOLS];
+} v2ce_voxmetrics_stats;
+size_t v2ce_voxmetrics_workspace_bytes(int B, int L, int C, int H, int W, const int *pool_sizes, int n_pools);
+int v2ce_voxmetrics(const float *pred, const float *gt, int B, int L, int C, int H, int W, float threshold,
+                    const int *pool_sizes, int n_pools, v2ce_voxmetrics_stats *stats, size_t stats_struct_size,
+                    void *workspace, size_t workspace_bytes, v2ce_stream_t stream);
+
+/* Batched, deterministic voxeliser (csrc/voxelize.hip): P event lists -> volume [P][2*bins][H][W] f32.  Events are SoA
+ * (timestamp int64, x, y int16, polarity int8); pair i owns events [offsets[i], offsets[i+1]) (int64 [P+1], monotone,
+ * within [0, n]).  Per pair the time range is its own [t_min, t_max], or t_range[i] = {t_min, t_max} (int64 [P][2],
+ * device, may be NULL).  The arithmetic of v2ce_voxelize_events; polarity <= 0 goes to planes [bins, 2*bins).  Every
+ * cell sums its floor contributions in event order, then its ceil contributions in event order, in f32 from zero:
+ * bit-identical to the serial put_(accumulate=True) of the reference.  status [P] int32 (device): bit 1 the pair is
+ * empty, 2 t_max == t_min, 4 an x / y outside the volume, 8 t_max < t_min (explicit range); a pair with any bit set
+ * gets a zero volume.  bins in [2, 16].  Workspace >= v2ce_voxelize_batch_workspace_bytes(P, bins, H, W, n), which
+ * returns 0 for arguments the entry refuses. */
+size_t v2ce_voxelize_batch_workspace_bytes(int P, int bins, int H, int W, int64_t n);
+int v2ce_voxelize_batch(const int64_t *ts, const int16_t *x, const int16_t *y, const int8_t *p, const int64_t *offsets,
+                        int64_t n, int P, int bins, int H, int W, const int64_t *t_range, float *volume,
+                        int32_t *status, void *workspace, size_t workspace_bytes, v2ce_stream_t stream);
+#define V2CE_VOXELIZE_EMPTY 1
+#define V2CE_VOXELIZE_SINGLE_TIMESTAMP 2
+#define V2CE_VOXELIZE_BAD_XY 4
+#define V2CE_VOXELIZE_BAD_RANGE 8
 
 /* One spectral-norm power iteration (spectral_norm.py:19-31), in place on u [rows], v [cols]:
  *   v = W^T u / (|W^T u| + 1e-12); u = W v / (|W v| + 1e-12); sigma = u . (W v)

@@ -35,6 +35,7 @@ EXPORTS = [
     "v2ce_conv3d_fwd_wt", "v2ce_conv3d_fwd_wt_tail", "v2ce_pack_weights_f16x2_wt", "v2ce_pack_weights_f16x2_wt_slice", "v2ce_conv3d_fwd_up2_part", "v2ce_pack_weights_f16x2_wt_bytes", "v2ce_conv3d_wt_variant",
     "v2ce_conv3d_head_f16x2", "v2ce_pack_head_weights_f16x2", "v2ce_pack_head_weights_f16x2_bytes", "v2ce_absmax_batch",
     "v2ce_tsdiff_workspace_bytes", "v2ce_tsdiff",
+    "v2ce_voxmetrics_workspace_bytes", "v2ce_voxmetrics", "v2ce_voxelize_batch_workspace_bytes", "v2ce_voxelize_batch",
 ]
 
 
@@ -74,6 +75,20 @@ class SamplerOptions(ctypes.Structure):
 
 
 SAMPLER_RANDOM, SAMPLER_EVEN, SAMPLER_PURE_SLOPE = 0, 1, 2
+
+VOXMETRICS_MAX_POOLS = 8
+
+
+class VoxMetricsStats(ctypes.Structure):
+    """``v2ce_voxmetrics_stats`` (include/v2ce_hip.h): the stage-1 sufficient statistics of one sequence."""
+    _fields_ = [("struct_size", ctypes.c_int64), ("n", ctypes.c_int64 * 3), ("tp", ctypes.c_int64 * 3),
+                ("fp", ctypes.c_int64 * 3), ("fn", ctypes.c_int64 * 3), ("abs_diff_sum", ctypes.c_double),
+                ("ratio_sum", ctypes.c_double), ("n_pools", ctypes.c_int64),
+                ("pool_size", ctypes.c_int64 * VOXMETRICS_MAX_POOLS), ("pool_n", ctypes.c_int64 * VOXMETRICS_MAX_POOLS),
+                ("pool_sq_sum", ctypes.c_double * VOXMETRICS_MAX_POOLS)]
+
+
+VOXELIZE_EMPTY, VOXELIZE_SINGLE_TIMESTAMP, VOXELIZE_BAD_XY, VOXELIZE_BAD_RANGE = 1, 2, 4, 8
 
 
 class V2ceHipError(RuntimeError):
@@ -209,6 +224,14 @@ def lib() -> ctypes.CDLL:
     L.v2ce_tsdiff_workspace_bytes.restype = sz
     L.v2ce_tsdiff.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
     L.v2ce_tsdiff.restype = ctypes.c_int
+    L.v2ce_voxmetrics_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, vp, i32]
+    L.v2ce_voxmetrics_workspace_bytes.restype = sz
+    L.v2ce_voxmetrics.argtypes = [vp, vp, i32, i32, i32, i32, i32, ctypes.c_float, vp, i32, vp, sz, vp, sz, vp]
+    L.v2ce_voxmetrics.restype = ctypes.c_int
+    L.v2ce_voxelize_batch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
+    L.v2ce_voxelize_batch_workspace_bytes.restype = sz
+    L.v2ce_voxelize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
+    L.v2ce_voxelize_batch.restype = ctypes.c_int
     for name in ("v2ce_ldati_count", "v2ce_ldati_emit", "v2ce_events_pack",
                  "v2ce_conv3d_fwd", "v2ce_conv3d_variant", "v2ce_pack_weights", "v2ce_sn_power_iter"):
         getattr(L, name).restype = ctypes.c_int

@@ -290,6 +290,13 @@ def build_parser():
     p.add_argument("-p", "--pooling_type", default="none", choices=["none", "weighted", "avg"])
     p.add_argument("--bidirectional", action="store_true", help="bidirectional y_relocate in LDATI")
     p.add_argument("--seed", type=int, default=42, help="Philox seed of the samplers")
+    # the stage-1 score (stage1_metrics.py): opt-in
+    p.add_argument("--stage1", action="store_true",
+                   help="also score voxel grids (BinaryMatch[F1], PoolMSE, L1, MeanRatio) against the GT voxelised per "
+                        "pair: writes stage1_result.csv and stage1_record.json")
+    p.add_argument("--pred_events", type=str, default=None,
+                   help="with --stage1: score this event stream (.npz event_stream or structured .npy), voxelised per "
+                        "pair like the GT, instead of the model's voxels; needs --frame_timestamps, skips stage 2")
     p.add_argument("-o", "--out_folder", type=str, default="./results")
     p.add_argument("-l", "--log_level", type=str, default="info")
     return p
@@ -331,6 +338,8 @@ def write_results(out_folder: str, summary: Dict[str, np.ndarray], records) -> N
 def main(argv=None):
     args = build_parser().parse_args(argv)
     logging.basicConfig(level=getattr(logging, args.log_level.upper()))
+    if args.pred_events is not None:
+        return _main_pred_events(args)
     from . import glue, synth
     from .v2ce import get_trained_mode, read_image_folder
     from .v2ce_3d import V2ce3d
@@ -369,6 +378,37 @@ def main(argv=None):
     for m, v in summary.items():
         logger.info(f"{m}: avg error {v[0]:.3f}, overflow {v[1]:.3f}, pred/gt {v[2]:.3f}")
     print(op.join(args.out_folder, "abbr_result.csv"))
+    if args.stage1:
+        from .stage1_metrics import run_stage1_metric
+        s1, r1 = run_stage1_metric(voxels, gt, counts, T, seq_len=args.seq_len)
+        _report_stage1(args.out_folder, s1, r1)
+
+
+def _report_stage1(out_folder, summary, records):
+    from .stage1_metrics import write_stage1_results
+    write_stage1_results(out_folder, summary, records)
+    for k, v in summary.items():
+        print(f"{k:22s} {v:.6f}")
+    print(op.join(out_folder, "stage1_result.csv"))
+
+
+def _main_pred_events(args):
+    """--stage1 --pred_events: an event stream against the recording, both voxelised per pair (no model, no stage 2)."""
+    from .stage1_metrics import run_stage1_metric
+    if not args.stage1:
+        raise SystemExit("--pred_events scores stage 1 only: give --stage1")
+    if args.frame_timestamps is None:
+        raise SystemExit("--pred_events needs --frame_timestamps")
+    T = np.load(args.frame_timestamps).astype(np.int64).reshape(-1)
+    gt, counts, dropped = split_by_frames(load_events(args.gt_events), T)
+    pred, pcounts, pdropped = split_by_frames(load_events(args.pred_events), T)
+    logger.info(f"{len(gt)} GT / {len(pred)} predicted events in {T.size - 1} pairs; {dropped} / {pdropped} dropped")
+    dev = torch.device(args.device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    s1, r1 = run_stage1_metric(None, gt, counts, T, seq_len=args.seq_len, pred_events=pred, pred_counts=pcounts,
+                               height=args.height, width=args.width, device=dev)
+    _report_stage1(args.out_folder, s1, r1)
 
 
 if __name__ == "__main__":
