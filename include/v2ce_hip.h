@@ -561,6 +561,40 @@ int v2ce_voxelize_batch(const int64_t *ts, const int16_t *x, const int16_t *y, c
 #define V2CE_VOXELIZE_BAD_XY 4
 #define V2CE_VOXELIZE_BAD_RANGE 8
 
+/* Event-frame video (csrc/event_frames.hip): the array work of write_event_frame_video (v2ce.py:253-269,275-276) on
+ * the device.  mode: V2CE_EVENT_FRAMES_POLARITY = keep_polarity=True (channels S0, S1 and a zero plane, float64
+ * arithmetic, v2ce.py:255-257), V2CE_EVENT_FRAMES_GREY = keep_polarity=False (S2 three times, float32, v2ce.py:259-260).
+ *
+ * v2ce_event_frames_sums: vox [P][2][10][H][W] f32 -> sums [P][3][H][W] f32: S0 / S1 = the ten bins of a polarity
+ *   added in plane order, S2 = all twenty planes added in plane order, each in f32 from the first plane on
+ *   (np.sum(axis=2) / np.sum(axis=(1,2)), v2ce.py:255,259).  hist (may be NULL): V2CE_EVENT_FRAMES_LEVEL0_BINS uint64
+ *   counters; counter (bits >> 20) of every value > 0 of the mode's channels (S0 and S1, or S2) is raised by one.
+ * v2ce_event_frames_refine: over stored sums, hist [2][V2CE_EVENT_FRAMES_REFINE_BINS] uint64: row r counts the values
+ *   > 0 of the mode's channels whose leading bits equal prefix_a (r = 0) / prefix_b (r = 1), by their next ten bits:
+ *   level 1: bits >> 20 == prefix (< 2048), counter (bits >> 10) & 1023; level 2: bits >> 10 == prefix (< 2^21),
+ *   counter bits & 1023.  Positive floats order like their bit patterns, so the three levels give the value at any
+ *   rank of the clip exactly (the two order statistics np.percentile interpolates, v2ce.py:262-264).
+ *   Both entries ADD to hist: the caller zeroes it once per clip (and per level), calls once per batch in any order;
+ *   counts are integers (LDS per workgroup, then one 64-bit atomic per non-empty bin), so they do not depend on the
+ *   batching or the run, and two partial histograms add up to the histogram of the union.
+ * v2ce_event_frames_render: frames [total_pairs][H][W][3] uint8 RGB (the base of the clip's buffer, 4-byte aligned);
+ *   pairs [first_pair, first_pair + P) are written from sums [P][3][H][W]:
+ *   (uint8) (min(max(x, 0), upper) / upper * 255), division and product rounded separately, in float64 with blue = 0
+ *   (polarity) or in float32 with upper rounded to float32 first (grey) (v2ce.py:267,276).  upper > 0, finite.
+ * P, H, W >= 1 else V2CE_ERR_BAD_ARG; H * W >= 2^28 or P * 20 * H * W >= 2^33 is V2CE_ERR_UNSUPPORTED.
+ * v2ce_event_frames_hist_bytes(level): bytes of the histogram of level 0 (sums), 1, 2 (refine); 0 for any other. */
+#define V2CE_EVENT_FRAMES_POLARITY 0
+#define V2CE_EVENT_FRAMES_GREY 1
+#define V2CE_EVENT_FRAMES_LEVEL0_BINS 2048
+#define V2CE_EVENT_FRAMES_REFINE_BINS 1024
+size_t v2ce_event_frames_hist_bytes(int level);
+int v2ce_event_frames_sums(const float *vox, int P, int H, int W, int mode, float *sums, uint64_t *hist,
+                           v2ce_stream_t stream);
+int v2ce_event_frames_refine(const float *sums, int P, int H, int W, int mode, int level, uint32_t prefix_a,
+                             uint32_t prefix_b, uint64_t *hist, v2ce_stream_t stream);
+int v2ce_event_frames_render(const float *sums, int P, int H, int W, int mode, double upper, int64_t first_pair,
+                             int64_t total_pairs, uint8_t *frames, v2ce_stream_t stream);
+
 /* One spectral-norm power iteration (spectral_norm.py:19-31), in place on u [rows], v [cols]:
  *   v = W^T u / (|W^T u| + 1e-12); u = W v / (|W v| + 1e-12); sigma = u . (W v)
  * w_bar [rows][cols] f32; sigma [1] f32 out; workspace >= v2ce_sn_workspace_bytes(rows, cols). */

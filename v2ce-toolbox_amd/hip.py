@@ -36,6 +36,7 @@ EXPORTS = [
     "v2ce_conv3d_head_f16x2", "v2ce_pack_head_weights_f16x2", "v2ce_pack_head_weights_f16x2_bytes", "v2ce_absmax_batch",
     "v2ce_tsdiff_workspace_bytes", "v2ce_tsdiff",
     "v2ce_voxmetrics_workspace_bytes", "v2ce_voxmetrics", "v2ce_voxelize_batch_workspace_bytes", "v2ce_voxelize_batch",
+    "v2ce_event_frames_hist_bytes", "v2ce_event_frames_sums", "v2ce_event_frames_refine", "v2ce_event_frames_render",
 ]
 
 
@@ -89,6 +90,9 @@ class VoxMetricsStats(ctypes.Structure):
 
 
 VOXELIZE_EMPTY, VOXELIZE_SINGLE_TIMESTAMP, VOXELIZE_BAD_XY, VOXELIZE_BAD_RANGE = 1, 2, 4, 8
+
+EVENT_FRAMES_POLARITY, EVENT_FRAMES_GREY = 0, 1
+EVENT_FRAMES_LEVEL0_BINS, EVENT_FRAMES_REFINE_BINS = 2048, 1024
 
 
 class V2ceHipError(RuntimeError):
@@ -232,6 +236,14 @@ def lib() -> ctypes.CDLL:
     L.v2ce_voxelize_batch_workspace_bytes.restype = sz
     L.v2ce_voxelize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
     L.v2ce_voxelize_batch.restype = ctypes.c_int
+    L.v2ce_event_frames_hist_bytes.argtypes = [i32]
+    L.v2ce_event_frames_hist_bytes.restype = sz
+    L.v2ce_event_frames_sums.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
+    L.v2ce_event_frames_sums.restype = ctypes.c_int
+    L.v2ce_event_frames_refine.argtypes = [vp, i32, i32, i32, i32, i32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    L.v2ce_event_frames_refine.restype = ctypes.c_int
+    L.v2ce_event_frames_render.argtypes = [vp, i32, i32, i32, i32, f64, i64, i64, vp, vp]
+    L.v2ce_event_frames_render.restype = ctypes.c_int
     for name in ("v2ce_ldati_count", "v2ce_ldati_emit", "v2ce_events_pack",
                  "v2ce_conv3d_fwd", "v2ce_conv3d_variant", "v2ce_pack_weights", "v2ce_sn_power_iter"):
         getattr(L, name).restype = ctypes.c_int

@@ -404,7 +404,7 @@ def run_clip(frames: np.ndarray, model, *, infer_type="center", seq_len=16, widt
              batch_size=1, fps=30, seed=0, device="cuda", stage2=None, dtype=None,
              comm=None, trace: Optional[dict] = None,
              reuse_output: bool = False, event_frames: Optional[list] = None, writer=None,
-             gather: Optional[str] = None) -> Optional[np.ndarray]:
+             gather: Optional[str] = None, event_frame_renderer=None) -> Optional[np.ndarray]:
     """frames [N,H,W] uint8 -> event_stream (structured array) on rank 0, None elsewhere.
 
     writer: an ``npz_stream.NpzStreamWriter`` (rank 0): the records go to the file batch by batch instead of into one
@@ -425,7 +425,9 @@ def run_clip(frames: np.ndarray, model, *, infer_type="center", seq_len=16, widt
     begin(vox, first_pair) -> handle; finish(handle) -> (packed uint8 tensor, keepalive).
     event_frames: a list that receives, per batch, (first pair, event_frame_sums(voxels)) on the device
     -- the reduction the reference's event-frame video starts from (v2ce.py:254-260); single-process
-    runs only."""
+    runs only.
+    event_frame_renderer: an ``event_frames.EventFrameRenderer`` that takes every batch's voxels instead
+    (``add(first pair, voxels)``: the sums stay on the device and it renders the frames there); single-process runs only."""
     from .LDATI import EVENT_DTYPE
     dtype = dtype or EVENT_DTYPE
     comm = comm or vdist.default_comm()
@@ -627,6 +629,8 @@ def run_clip(frames: np.ndarray, model, *, infer_type="center", seq_len=16, widt
                 first_pair += p_lo
         if event_frames is not None and vox is not None:
             event_frames.append((first_pair, event_frame_sums(vox)))
+        if event_frame_renderer is not None and vox is not None and vox.shape[0]:
+            event_frame_renderer.add(first_pair, vox)
         if tile_parallel:
             handle = guarded(begin, vox, first_pair) if vox is not None and vox.shape[0] else None
             return (handle, 0 if vox is None else int(vox.shape[0]))

@@ -186,6 +186,12 @@ def write_event_frame_video(efs: np.ndarray, ef_video_path, fps, ceil, upper_bou
     'mp4v'), which the build image lacks -- then the same uint8 frames are written next to it as
     ``<stem>.npz`` (key ``event_frames``, RGB)."""
     frames = event_frame_images(efs, ceil, upper_bound_percentile, keep_polarity)
+    return write_event_frame_container(frames, ef_video_path, fps)
+
+
+def write_event_frame_container(frames: np.ndarray, ef_video_path, fps):
+    """v2ce.py:272-280 for frames that are already uint8 RGB [L,H,W,3] (``event_frame_images`` on the host or
+    ``event_frames.EventFrameRenderer`` on the device): the mp4, or the ``.npz`` where OpenCV is missing."""
     try:
         import cv2
     except ImportError:
@@ -204,7 +210,8 @@ def write_event_frame_video(efs: np.ndarray, ef_video_path, fps, ceil, upper_bou
 
 def run(frames: np.ndarray, model, infer_type="center", seq_len=16, width=346, height=260,
         batch_size=1, fps=30, stage2_batch_size=24, seed=0, rng="philox", device="cuda",
-        stage2=None, event_frames: Optional[list] = None, comm=None, out_path: Optional[str] = None):
+        stage2=None, event_frames: Optional[list] = None, comm=None, out_path: Optional[str] = None,
+        event_frame_renderer=None):
     """frames [N,H,W] uint8 -> event_stream (numpy structured array, v2ce.py:368) on rank 0.
 
     out_path (Philox draws only): write the reference's ``np.savez(out_path, event_stream=...)`` file WHILE the clip
@@ -215,7 +222,10 @@ def run(frames: np.ndarray, model, infer_type="center", seq_len=16, width=346, h
     UNet + LDATI, D2H overlapped; under torch.distributed sharded over GPUs).  ``rng='torch'``
     reproduces the reference's structure instead -- the whole clip through the model, then LDATI in
     chunks of --stage2_batch_size with one dense torch.rand per chunk (LDATI.py:169-171) -- because
-    that draw order depends on the chunking."""
+    that draw order depends on the chunking.
+
+    event_frame_renderer (single-process device runs): an ``event_frames.EventFrameRenderer`` fed with every batch's
+    voxels; the caller takes the video's frames from its ``finish()``."""
     from . import pipeline
     comm = comm or vdist.default_comm(force=os.environ.get("V2CE_FORCE_DIST") == "1")
     world = comm.world
@@ -230,12 +240,17 @@ def run(frames: np.ndarray, model, infer_type="center", seq_len=16, width=346, h
                 from .pipeline import event_frame_sums
                 del event_frames[:]
                 event_frames.append((0, event_frame_sums(vox)))
+            if event_frame_renderer is not None:
+                event_frame_renderer.reset()
+                event_frame_renderer.add(0, vox)
             packed, _ = events_from_voxels(vox, fps, stage2_batch_size, seed, rng)
             return download_events(packed)
     else:
         def clip():
             if event_frames is not None:
                 del event_frames[:]
+            if event_frame_renderer is not None:
+                event_frame_renderer.reset()
             writer = None
             if out_path is not None and comm.rank == 0:     # (a range-guard rerun of the clip starts the file again)
                 from .npz_stream import NpzStreamWriter
@@ -243,7 +258,8 @@ def run(frames: np.ndarray, model, infer_type="center", seq_len=16, width=346, h
             out = pipeline.run_clip(frames, model, infer_type=infer_type, seq_len=seq_len, width=width, height=height,
                                     batch_size=batch_size, fps=fps, seed=seed, device=device, stage2=stage2,
                                     dtype=EVENT_DTYPE, comm=comm, writer=writer,
-                                    event_frames=event_frames if world == 1 else None)
+                                    event_frames=event_frames if world == 1 else None,
+                                    event_frame_renderer=event_frame_renderer if world == 1 else None)
             return writer.count if writer is not None else out
     # the split-half convolutions report a dynamic-range bound; beyond its limit the clip is repeated on
     # the exact-f32 kernels (glue.run_guarded)
@@ -294,14 +310,26 @@ def main(argv=None):
         model = model.eval().to(device)
     else:
         model = get_trained_mode(args.model_path, device, args.precision)
-    efs = [] if (args.write_event_frame_video and world == 1) else None
+    # the video's frames come from the device (event_frames.py) on single-process GPU runs; V2CE_EVENT_FRAMES=host and
+    # --device cpu keep the host path (sums downloaded, numpy)
+    renderer = None
+    if (args.write_event_frame_video and world == 1 and torch.device(device).type == "cuda"
+            and os.environ.get("V2CE_EVENT_FRAMES", "device") != "host"):
+        from .event_frames import EventFrameRenderer
+        renderer = EventFrameRenderer(args.vis_keep_polarity, args.ceil, args.upper_bound_percentile, args.height, None, device)
+    efs = [] if (args.write_event_frame_video and world == 1 and renderer is None) else None
     if args.write_event_frame_video and world > 1:
         logger.warning("the event-frame video (v2ce.py:241-280) is written by single-process runs only: skipped")
     events_path = op.join(args.out_folder, f"{output_name}-events.npz")
     streaming = args.stream_events and args.rng == "philox"
     event_stream = run(frames, model, args.infer_type, args.seq_len, args.width, args.height,
                        args.batch_size, args.fps, args.stage2_batch_size, args.seed, args.rng, device,
-                       event_frames=efs, out_path=events_path if streaming else None)
+                       event_frames=efs, out_path=events_path if streaming else None, event_frame_renderer=renderer)
+    if renderer is not None:
+        ef_frames, _ = renderer.finish()
+        vis_color = "rgb" if args.vis_keep_polarity else "gray"
+        write_event_frame_container(ef_frames, op.join(args.out_folder, f"{args.infer_type}-{output_name}-pred_ef_{vis_color}.mp4"),
+                                    args.fps)
     if efs:
         ef = torch.cat([t for _, t in sorted(efs, key=lambda kv: kv[0])]).cpu().numpy()
         vis_color = "rgb" if args.vis_keep_polarity else "gray"
