@@ -435,50 +435,38 @@ def test_dense_tile_kernel_equals_per_bin_kernel(gold_dir, monkeypatch):
     assert hashlib.sha256(ev.to_recarrays()[0].tobytes()).hexdigest() == meta["sha256_packed_events"]
 
 
-@pytest.mark.parametrize("form", ["V2CE_LDATI_PAIR", "V2CE_LDATI_ONEPASS"])
-def test_pair_pass_kernel_equals_per_bin_kernel(form, monkeypatch):
-    """ldati_tile_pair_kernel (round 6: two bins of a dense tile per pass where their records share the LDS; V2CE_LDATI_PAIR=1) and
-    ldati_tile_onepass_kernel (the classification of all nine bins in one sweep, the work lists in global scratch, pair passes
-    behind it; V2CE_LDATI_ONEPASS=1) against the per-bin dense kernel (the default): same bytes and the oracle's events -- on Philox stress frames (pairs 0-1 .. 6-7
-    and bin 8 alone in the 16-wave form), at half and quarter that density (the 8-wave form, two workgroups per CU; at the
-    lower density every pass is a pair), on a tile mix where pairs and single-bin passes alternate (a bin that fits with
-    neither neighbour), with a voxel outside the slope table in either bin of a pair, at 60 fps with a start time, through the
-    two-pass path (fused count off) and the dense slot mode (second call of a stream) alike."""
+def test_dense_tile_kernel_two_pass_and_slot_mode_equal_oracle(monkeypatch):
+    """ldati_tile_dense_kernel on the inputs that used to pit it against the removed two-bins-per-pass forms: the oracle's events
+    and the same bytes from the two-pass path (first call of a stream) and the dense slot mode (second call) -- on Philox stress
+    frames (the 16-wave form), at half and quarter that density (the 8-wave form, two workgroups per CU), on a tile mix of
+    bins of very different weight with a voxel outside the slope table in a light bin and in a heavy one and an empty
+    stretch, at 60 fps with a start time, and with the fused count off."""
     from v2ce_toolbox_amd import LDATI
-
-    def both(run):
-        monkeypatch.setenv(form, "1")                          # (both forms are opt-in: DESIGN 4.2 round 6)
-        a = run()
-        monkeypatch.delenv(form)
-        b = run()
-        assert np.array_equal(a.seg_counts, b.seg_counts)
-        assert a.packed().cpu().numpy().tobytes() == b.packed().cpu().numpy().tobytes()
-        return a
 
     for scale, seed in ((6.0, 5), (3.0, 6), (1.5, 7)):
         vox = (scale * np.random.default_rng(seed).random((2, 2, 10, 260, 346))).astype(np.float32)
         LDATI._SEG_HINT.clear()
-        ev = both(lambda: hip_events(vox, seed=31 + seed, frame_base=3))           # first call of a stream: the two-pass path
-        ev2 = both(lambda: hip_events(vox, seed=31 + seed, frame_base=3))          # second call: the dense kernel is the count pass
+        ev = hip_events(vox, seed=31 + seed, frame_base=3)           # first call of a stream: the two-pass path
+        ev2 = hip_events(vox, seed=31 + seed, frame_base=3)          # second call: the dense kernel is the count pass
         assert ev.packed().cpu().numpy().tobytes() == ev2.packed().cpu().numpy().tobytes()
         seg, ts, x, y, p = O.emit_soa(vox[:1], fps=30, seed=31 + seed, frame_base=3)
         n0 = int(seg.sum())
         assert np.array_equal(ev.seg_counts[:1], seg) and np.array_equal(ev.ts.cpu().numpy()[:n0], ts)
         assert np.array_equal(ev.x.cpu().numpy()[:n0], x) and np.array_equal(ev.y.cpu().numpy()[:n0], y)
         assert np.array_equal(ev.p.cpu().numpy()[:n0], p)
-    # bins of very different weight: pairs where two light bins meet, single passes around the heavy ones
+    # bins of very different weight
     rng = np.random.default_rng(11)
     mix = (rng.random((2, 2, 10, 128, 160)) * np.array([1, 9, 1, 1, 12, 12, 1, 0.2, 5, 3], np.float32)[None, None, :, None, None]).astype(np.float32)
-    mix[0, 0, 4, 50, 7] = 45.0                                    # count 45 > 31: outside the slope table, second bin of a pair
-    mix[1, 1, 2, 70, 9] = 60.0                                    # ... and the first bin of one
-    mix[1, 0, :, :40] = 0.0                                       # an empty stretch: bins without a record inside a pass
+    mix[0, 0, 4, 50, 7] = 45.0                                    # count 45 > 31: outside the slope table, in a heavy bin
+    mix[1, 1, 2, 70, 9] = 60.0                                    # ... and in a light one
+    mix[1, 0, :, :40] = 0.0                                       # an empty stretch: bins without a record
     for fps, t0 in ((30, 0), (60, 0.5)):
         LDATI._SEG_HINT.clear()
         for _ in range(2):
-            soa_equal(both(lambda: hip_events(mix, fps, t0, seed=77, frame_base=1)), *O.emit_soa(mix, fps=fps, t0=t0, seed=77, frame_base=1))
+            soa_equal(hip_events(mix, fps, t0, seed=77, frame_base=1), *O.emit_soa(mix, fps=fps, t0=t0, seed=77, frame_base=1))
     # the fused count switched off: tile offsets from the count pass instead of slots
     monkeypatch.setenv("V2CE_LDATI_NO_FUSED", "1")
-    soa_equal(both(lambda: hip_events(mix, seed=78)), *O.emit_soa(mix, fps=30, seed=78))
+    soa_equal(hip_events(mix, seed=78), *O.emit_soa(mix, fps=30, seed=78))
     monkeypatch.delenv("V2CE_LDATI_NO_FUSED")
 
 

@@ -36,7 +36,7 @@
 #endif
 #include <type_traits>
 
-// producer-side epilogue (conv3d_f16x2_ws_kernel, OPT bit 0): position fragments per wave whose epilogue stays with the consumers
+// producer-side epilogue (conv3d_f16x2_ws_kernel, OPT 1): position fragments per wave whose epilogue stays with the consumers
 // (measured on dec3.conv2 + head: 2 of 4 -> 0.94 ms, 1 of 4 -> 0.98, 0 of 4 -> 0.99, all four = no hand-over -> 1.01)
 #ifndef V2CE_PEPI_KEEP
 #define V2CE_PEPI_KEEP 2
@@ -357,7 +357,7 @@ __global__ __launch_bounds__(256, MW) void conv3d_kernel(ConvParams P) {
 //       4 = 3 + 1 (round 6): the folded tail AND the fused head -- conv2 of the last decoder block with its shortcut split by source:
 //           the skip channels ride as the tail, the upsampled channels' share arrives as a low-resolution residual (P.res_up)
 // RES: residual known at compile time (0 = none, 1 = present) or checked at run time (2), see conv_epilogue
-// OPT bit 0, "PEPI" (round 6): the tile's epilogue is SHARED between the roles.  The 32-channel tile with the fused head has two chunks
+// OPT 1, "PEPI" (round 6): the tile's epilogue is SHARED between the roles.  The 32-channel tile with the fused head has two chunks
 //       of 324 MFMAs per wave and an epilogue (residual, scale / shift, ReLU, the head's MFMAs, 20 planar channels of stores) that
 //       took 17-19 k of its 46 k cycles with the producers idle at barriers for half of the launch.  Now the consumers leave the
 //       accumulators of V2CE_PEPI_KEEP .. PO_FR - 1 of a wave's position fragments in the pieces buffer the tile's last chunk has just
@@ -370,22 +370,16 @@ __global__ __launch_bounds__(256, MW) void conv3d_kernel(ConvParams P) {
 template <int KS, int S, int WCO, int CO_FR, int PO_FR, int NA, int FUSE = 0, int RES = 2, int OPT = 0>
 __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int PEPI = OPT & 1;                              // (OPT: a bit set; bit 0 = the producer-side epilogue)
-    // bit 1, "G4": the producers gather with FOUR LANES PER ELEMENT -- load instruction k of a quad of lanes fetches the four 16-byte
-    // quarters of the element lane k of the quad owns (its offset arrives by a quad broadcast), so an instruction touches 16 whole
-    // 64-byte lines instead of a quarter of each of 64: the texture path the consumers' weight loads share is what the gather
-    // occupies.  A lane then holds four channels of four elements instead of sixteen of one: 8-byte pieces.
-    constexpr bool G4 = (OPT & 2) != 0;
-    static_assert(!G4 || (KS == 3 && FUSE != 3 && FUSE != 4), "four-lane gather: plain 3x3x3 chunks (no folded tail)");
+    static_assert(OPT == 0 || OPT == 1, "OPT: 1 = the producer-side epilogue");
+    constexpr int PEPI = OPT;
     // KS = 1: the "halo box" is the output box itself (positions gathered with stride S), one tap
     constexpr int K3 = KS * KS * KS, CK = 16, EPT = 5, PAD = KS / 2, GS = KS == 1 ? S : 1;
     constexpr int CO_TILE = WCO * CO_FR * 32;
-    static_assert(!PEPI || ((FUSE == 1 || FUSE == 2) && CO_FR == 1),
-                  "shared epilogue: one 32-channel fragment row per wave, with the fused head or the fused shortcut");
+    static_assert(!PEPI || (FUSE == 1 && CO_FR == 1), "shared epilogue: one 32-channel fragment row per wave, with the fused head");
     // PEPI: the consumers keep the first kKeepFr position fragments of a wave for their own epilogue and hand the others over -- the
     // two epilogues run side by side between the tile's last chunk and the next tile's first
-    constexpr int kKeepFr = PEPI ? (FUSE == 1 ? V2CE_PEPI_KEEP : PO_FR / 2) : PO_FR, kDumpFr = PO_FR - kKeepFr;
-    constexpr int kDumpSets = FUSE == 2 ? 2 : 1;             // (the fused shortcut's second accumulator set travels too)
+    constexpr int kKeepFr = PEPI ? V2CE_PEPI_KEEP : PO_FR, kDumpFr = PO_FR - kKeepFr;
+    constexpr int kDumpSets = 1;                             // accumulator sets of a fragment that travel
     constexpr int kDumpWave = kDumpFr * kDumpSets * 4 * 64;  // f32x4 per consumer wave in the accumulator dump (PEPI)
     int chs_ = (FUSE == 3 || FUSE == 4) ? P.tCHS : (P.plane + 63) & ~63;
     if (PEPI && chs_ < kDumpWave) chs_ = kDumpWave;          // a pieces buffer (4 chs x 16 B) holds the four waves' dumps
@@ -394,16 +388,6 @@ __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
     [[maybe_unused]] unsigned *pepi_flag = reinterpret_cast<unsigned *>(conv_smem + (size_t)chs * 128);   // PEPI: producer waves done reading a dump
     if constexpr (PEPI != 0) {                               // (all of it visible behind the first chunk barrier, long before its first use)
         // LDS behind the pieces, 16 B in: scale[32] shift[32] of the conv, bias[32] of the head | the head's A fragments (4 KB)
-        // -- or (fused shortcut) scale[Cout] | shift[Cout] | sc_scale[Cout] | sc_shift[Cout]
-        if constexpr (FUSE == 2) {
-            float *tab = reinterpret_cast<float *>(pepi_flag + 4);
-            for (int i = threadIdx.x; i < P.Cout; i += 512) {
-                tab[i] = P.scale[i];
-                tab[P.Cout + i] = P.shift[i];
-                tab[2 * P.Cout + i] = P.sc_scale[i];
-                tab[3 * P.Cout + i] = P.sc_shift[i];
-            }
-        } else {
         if (threadIdx.x < 32) {
             float *tab = reinterpret_cast<float *>(pepi_flag + 4);
             tab[threadIdx.x] = P.scale[threadIdx.x];
@@ -411,7 +395,6 @@ __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
             tab[64 + threadIdx.x] = P.pred_b[threadIdx.x];
         }
         if (threadIdx.x < 256) reinterpret_cast<f16x8 *>(pepi_flag + 100)[threadIdx.x] = reinterpret_cast<const f16x8 *>(P.pred_w)[threadIdx.x];
-        }
     }
 
     const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31, half = lane >> 5;
@@ -564,7 +547,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
     // tile by the caller (scalar loads whose round trip would otherwise open every fragment)
     [[maybe_unused]] auto epi_fragment = [&](const TileId &E, int f, const f32x4d (&a)[4], const f32x4d (&rv)[4], unsigned &ymax,
                                              float inv, float pw_scale, auto &&between) __attribute__((always_inline)) {
-        if constexpr (PEPI != 0 && FUSE == 1) {
+        if constexpr (PEPI != 0) {
             typedef unsigned u32x4d __attribute__((ext_vector_type(4)));
             const float *tab = reinterpret_cast<const float *>(pepi_flag + 4);                      // scale[32] | shift[32] | bias[32]
             const f16x8 *atab = reinterpret_cast<const f16x8 *>(pepi_flag + 100);                   // the head's A fragments (4 KB)
@@ -667,55 +650,6 @@ __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
         }
     };
 
-    // the same for the conv with the fused shortcut (FUSE 2): y = act(scale a + shift), sc_y = sc_scale ad + sc_shift, both in the
-    // channels-last-16 layout (one 16-byte store per register quad and output)
-    [[maybe_unused]] auto epi_fragment_sc = [&](const TileId &E, int f, const f32x4d (&a)[4], const f32x4d (&ad)[4], unsigned &ymax) __attribute__((always_inline)) {
-        if constexpr (PEPI != 0 && FUSE == 2) {
-            typedef unsigned u32x4d __attribute__((ext_vector_type(4)));
-            const int co0 = E.co_t * CO_TILE + ((wave & 3) % WCO) * 32;
-            const long long wpl_d = (long long)CG * P.Cout * 16;
-            const float xs = scale_of(E.b);
-            const float inv = 1.0f / (xs * w_scale), invd = 1.0f / (xs * reinterpret_cast<const float *>(P.sc_w + 2 * wpl_d)[1]);
-            const float *tab = reinterpret_cast<const float *>(pepi_flag + 4);
-            const long long seq = (long long)P.T * P.Cout * (P.Hout * P.Woutp);
-            const int gstride = P.Hout * P.Woutp * 64;            // bytes between 16-channel groups of a time step
-            const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(P.y + E.b * seq, 0, (int)(seq * 4), 0x00020000);
-            const __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc(P.sc_y + E.b * seq, 0, (int)(seq * 4), 0x00020000);
-            const float slope = act_slope(P.act);
-            unsigned vo, vp;
-            epi_offsets(E, f, vo, vp);
-            const unsigned vmask = vo != kOOB ? 0x7fffffffu : 0u;
-            f32x4d scq[4], shq[4], dq[4], dsh[4];                 // one LDS round trip
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const int cb = co0 + 8 * r4 + 4 * half;
-                scq[r4] = *reinterpret_cast<const f32x4d *>(tab + cb);
-                shq[r4] = *reinterpret_cast<const f32x4d *>(tab + P.Cout + cb);
-                dq[r4] = *reinterpret_cast<const f32x4d *>(tab + 2 * P.Cout + cb);
-                dsh[r4] = *reinterpret_cast<const f32x4d *>(tab + 3 * P.Cout + cb);
-            }
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const bool cok = co0 + 8 * r4 < P.Cout;            // uniform (Cout need not fill the last channel tile)
-                const int so = (co0 / 16 + (r4 >> 1)) * gstride + 32 * (r4 & 1);
-                f32x4d y4, d4;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float t = a[r4][k] * (scq[r4][k] * inv) + shq[r4][k];
-                    t = apply_act(t, slope);
-                    y4[k] = t;
-                    const unsigned av = __builtin_bit_cast(unsigned, t) & (cok ? vmask : 0u);
-                    ymax = av > ymax ? av : ymax;
-                    d4[k] = ad[r4][k] * (dq[r4][k] * invd) + dsh[r4][k];
-                }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4d, y4), rs_y, cok ? vo : kOOB, so, 0);
-                asm volatile("s_nop 1" : "+v"(y4));            // (16-byte store data hazard: conv_epilogue)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4d, d4), rs_s, cok ? vo : kOOB, so, 0);
-                asm volatile("s_nop 1" : "+v"(d4));
-            }
-        }
-    };
-
     if (wave >= 4) {
         // ------------------------------------------------------------------ producers
         // a chunk travels global -> registers (gather with the halo offsets; out-of-range offsets
@@ -789,16 +723,6 @@ __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
                     // the chunk is one 16-channel group: the element's 64 bytes in four 16-byte loads (one cache
                     // line per element; the planar layout needs 16 loads from 16 lines)
                     typedef float f32x4g __attribute__((ext_vector_type(4)));
-                    if constexpr (G4) {
-                        // R[4 k + c][i] = channel 4 (lane & 3) + c of the element that lane k of this lane's quad owns
-                        const int so = ((ci0 - src_cbase) / 16) * (src_cstride4 * 16);
-                        step_loop<0, 4>([&](auto kc) {
-                            constexpr int k = decltype(kc)::value;
-                            const unsigned vk = (unsigned)__builtin_amdgcn_mov_dpp((int)vo, k | (k << 2) | (k << 4) | (k << 6), 0xf, 0xf, true);
-                            const f32x4g v = __builtin_bit_cast(f32x4g, __builtin_amdgcn_raw_buffer_load_b128(rs_in, vk + 16u * (unsigned)(ptid & 3), so, 0));
-                            R[4 * k][i] = v[0]; R[4 * k + 1][i] = v[1]; R[4 * k + 2][i] = v[2]; R[4 * k + 3][i] = v[3];
-                        });
-                    } else
 #pragma unroll
                     for (int k4 = 0; k4 < CK / 4; ++k4) {
                         const f32x4g v = __builtin_bit_cast(f32x4g, __builtin_amdgcn_raw_buffer_load_b128(
@@ -839,33 +763,6 @@ __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
                 if (i >= ne_abl) continue;
 #endif
                 const int r = rb + 256 * i;
-                if constexpr (G4) {
-                    if ((wave - 4) * 64 + 256 * i < lim) {            // wave-uniform
-                        // this lane's four channels 4 j .. 4 j + 3 (j = lane & 3) of the quad's four elements: 8 bytes of the hi piece and
-                        // 8 of the lo piece of 8-channel group j >> 1, second half of the piece for odd j
-                        typedef unsigned u32x2c __attribute__((ext_vector_type(2)));
-                        const int j = rb & 3;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            u32x2c ph, pl;
-#pragma unroll
-                            for (int c2 = 0; c2 < 2; ++c2) {
-                                const float xa = R[4 * k + 2 * c2][i], xb = R[4 * k + 2 * c2 + 1][i];
-                                unsigned h, l;
-                                asm("v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
-                                    "v_fma_mixhi_f16 %0, %3, %4, 0\n\t"
-                                    "v_fma_mixlo_f16 %1, %2, %4, -%0 op_sel_hi:[0,0,1]\n\t"
-                                    "v_fma_mixhi_f16 %1, %3, %4, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-                                    : "=&v"(h), "=&v"(l) : "v"(xa), "v"(xb), "v"(c_scale));
-                                ph[c2] = h;
-                                pl[c2] = l;
-                            }
-                            const int rk = (r & ~3) + k;
-                            reinterpret_cast<u32x2c *>(qb + (j >> 1) * chs + rk)[j & 1] = ph;
-                            reinterpret_cast<u32x2c *>(qb + (2 + (j >> 1)) * chs + rk)[j & 1] = pl;
-                        }
-                    }
-                } else
                 if ((wave - 4) * 64 + 256 * i < lim) {                // wave-uniform (lanes past the box write padding)
 #pragma unroll
                     for (int hg = 0; hg < 2; ++hg) {
@@ -918,26 +815,16 @@ __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
             if constexpr (PEPI != 0) {
                 const f32x4d *dump = reinterpret_cast<const f32x4d *>(pieces + (g_last & 1) * 4 * chs) + (wave - 4) * kDumpWave;
                 unsigned ymax = 0u;
-                [[maybe_unused]] float inv = 1.0f, pw_scale = 1.0f;
-                if constexpr (FUSE == 1) {
-                    inv = 1.0f / (scale_of(E.b) * w_scale);
-                    pw_scale = reinterpret_cast<const float *>(P.pred_w + 2048)[0];
-                }
+                const float inv = 1.0f / (scale_of(E.b) * w_scale);
+                const float pw_scale = reinterpret_cast<const float *>(P.pred_w + 2048)[0];
                 step_loop<kKeepFr, PO_FR>([&](auto fc) {
                     constexpr int f = decltype(fc)::value;   // the wave's fragment; its accumulators are fragment f - kKeepFr of the dump
                     f32x4d a[4];
 #pragma unroll
                     for (int r4 = 0; r4 < 4; ++r4) a[r4] = dump[(((f - kKeepFr) * kDumpSets) * 4 + r4) * 64 + lane];
-                    if constexpr (FUSE == 2) {
-                        f32x4d ad[4];
-#pragma unroll
-                        for (int r4 = 0; r4 < 4; ++r4) ad[r4] = dump[(((f - kKeepFr) * kDumpSets + 1) * 4 + r4) * 64 + lane];
-                        epi_fragment_sc(E, f, a, ad, ymax);
-                    } else {
-                        epi_fragment(E, f, a, epi_rv, ymax, inv, pw_scale, [&]() __attribute__((always_inline)) {
-                            if constexpr (f + 1 < PO_FR) epi_load_res(E, f + 1, epi_rv);
-                        });
-                    }
+                    epi_fragment(E, f, a, epi_rv, ymax, inv, pw_scale, [&]() __attribute__((always_inline)) {
+                        if constexpr (f + 1 < PO_FR) epi_load_res(E, f + 1, epi_rv);
+                    });
                     __builtin_amdgcn_sched_barrier(0);
                 });
                 if (P.y_absmax) absmax_commit(__builtin_bit_cast(float, ymax), P.y_absmax + E.b * P.amax_bs);
@@ -1268,8 +1155,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
             // the producers run the epilogue of this wave's fragments kKeepFr .. PO_FR - 1 (tile_epilogue) out of the buffer of the tile's
             // last chunk, this wave the others', side by side
             [[maybe_unused]] const unsigned long long td = TICK();
-            [[maybe_unused]] float pw_scale_c = 1.0f;
-            if constexpr (FUSE == 1) pw_scale_c = reinterpret_cast<const float *>(P.pred_w + 2048)[0];
+            const float pw_scale_c = reinterpret_cast<const float *>(P.pred_w + 2048)[0];
             f32x4d rvK[kKeepFr][4];                             // the residual of this wave's own fragments, requested in front of the hand-over
 #pragma unroll
             for (int f = 0; f < kKeepFr; ++f) epi_load_res(T, f, rvK[f]);
@@ -1278,11 +1164,8 @@ __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
 #pragma unroll
             for (int f = kKeepFr; f < PO_FR; ++f)
 #pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) {
+                for (int r4 = 0; r4 < 4; ++r4)
                     dump[(((f - kKeepFr) * kDumpSets) * 4 + r4) * 64 + lane] = f32x4d{acc[0][f][4 * r4], acc[0][f][4 * r4 + 1], acc[0][f][4 * r4 + 2], acc[0][f][4 * r4 + 3]};
-                    if constexpr (SC)
-                        dump[(((f - kKeepFr) * kDumpSets + 1) * 4 + r4) * 64 + lane] = f32x4d{accd[0][f][4 * r4], accd[0][f][4 * r4 + 1], accd[0][f][4 * r4 + 2], accd[0][f][4 * r4 + 3]};
-                }
             lds_barrier();                                      // the producers may start
             ACC_T(tc_dump, td);
             {
@@ -1293,12 +1176,6 @@ __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
                     f32x4d a[4];
 #pragma unroll
                     for (int r4 = 0; r4 < 4; ++r4) a[r4] = f32x4d{acc[0][f][4 * r4], acc[0][f][4 * r4 + 1], acc[0][f][4 * r4 + 2], acc[0][f][4 * r4 + 3]};
-                    if constexpr (SC) {
-                        f32x4d ad[4];
-#pragma unroll
-                        for (int r4 = 0; r4 < 4; ++r4) ad[r4] = f32x4d{accd[0][f][4 * r4], accd[0][f][4 * r4 + 1], accd[0][f][4 * r4 + 2], accd[0][f][4 * r4 + 3]};
-                        epi_fragment_sc(T, f, a, ad, ymax);
-                    } else
                     epi_fragment(T, f, a, rvK[f], ymax, out_inv_scale, pw_scale_c, []() {});
                     __builtin_amdgcn_sched_barrier(0);
                 });
@@ -1335,7 +1212,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
 #ifdef V2CE_ABLATE_EPI
         if (P.ablate != 1)
 #endif
-        if constexpr (SC && PEPI == 0) {                        // shortcut: bn_d(conv_d x), no activation, no residual
+        if constexpr (SC) {                                     // shortcut: bn_d(conv_d x), no activation, no residual
             ConvParams Q = P;
             Q.scale = P.sc_scale; Q.shift = P.sc_shift; Q.res = nullptr; Q.y = P.sc_y; Q.act = V2CE_ACT_NONE;
             Q.y_absmax = nullptr;
@@ -1675,10 +1552,10 @@ __global__ __launch_bounds__(256) void weights_absmax_kernel(const float *__rest
 
 template <int KS, int S, int WCO, int CO_FR, int PO_FR, int NA, int FUSE = 0, int RES = 2, int OPT = 0>
 int launch_f16x2_ws(ConvParams P, const v2ce_conv3d_desc &d, hipStream_t stream) {
-    constexpr int PEPI = OPT & 1;
+    constexpr int PEPI = OPT;
     static_assert(27 % NA == 0 && NA >= 2, "the A-fragment ring must divide the 27 taps");
     constexpr int CO_TILE = WCO * CO_FR * 32, POS_TILE = (4 / WCO) * PO_FR * 32;
-    constexpr int MAX_PLANE = PEPI ? 1152 : 1280;      // 128 B of LDS per halo element; 5 elements per producer lane (PEPI: + up to 8.2 KB of tables)
+    constexpr int MAX_PLANE = PEPI ? 1152 : 1280;      // 128 B of LDS per halo element; 5 elements per producer lane (PEPI: + 4.4 KB of tables)
     if (g_name_out) {
         snprintf(g_name_out, g_name_cap, "conv3d_f16x2_ws_kernel<%d,%d,%d,%d,%d,%d,%d,%d,%d>", KS, S, WCO, CO_FR, PO_FR, NA, FUSE, RES, OPT);
         return V2CE_OK;
@@ -1718,12 +1595,10 @@ int launch_f16x2_ws(ConvParams P, const v2ce_conv3d_desc &d, hipStream_t stream)
         P.tCHS = chs;
     }
     if (PEPI) {                             // a pieces buffer doubles as the accumulator dump of the four consumer waves (16 B x 64 lanes per register quad)
-        constexpr int keep = FUSE == 1 ? V2CE_PEPI_KEEP : PO_FR / 2;
-        constexpr int dump = (PO_FR - keep) * (FUSE == 2 ? 2 : 1) * 4 * 64;     // (kDumpWave of the kernel)
+        constexpr int dump = (PO_FR - V2CE_PEPI_KEEP) * 4 * 64;     // (kDumpWave of the kernel)
         chs = chs > dump ? chs : dump;
-        V2CE_REQUIRE(FUSE == 1 || d.Cout <= 512, V2CE_ERR_UNSUPPORTED, "v2ce_conv3d_fwd(f16x2 ws, shared epilogue): more than 512 output channels");
     }
-    const size_t lds = (size_t)chs * (2 * 4 * 16) + (PEPI ? (FUSE == 1 ? 400 + 4096 : 16 + 16 * (size_t)d.Cout) : 0);   // (PEPI: + the epilogue's tables)
+    const size_t lds = (size_t)chs * (2 * 4 * 16) + (PEPI ? 400 + 4096 : 0);   // (PEPI: + the epilogue's tables)
     V2CE_REQUIRE(lds <= 160 * 1024, V2CE_ERR_UNSUPPORTED, "v2ce_conv3d_fwd(f16x2 ws): %zu B of LDS", lds);
     auto kern = conv3d_f16x2_ws_kernel<KS, S, WCO, CO_FR, PO_FR, NA, FUSE, RES, OPT>;
     V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
@@ -1999,9 +1874,6 @@ static int conv3d_dispatch(const v2ce_conv3d_desc *desc, const float *x0, const 
             // (round 6: its epilogue on the producer waves; V2CE_PEPI=0: the consumers' own)
             static const bool pepi = [] { const char *e = getenv("V2CE_PEPI"); return !(e && e[0] == '0'); }();
             // (nine ring slots: the consumers' path has the registers -- the 229 of the kernel are the producers' -- 0.94 -> 0.91 ms)
-            static const bool g4s = [] { const char *e = getenv("V2CE_G4"); return e && e[0] == '1'; }();
-            if (small_co && P.pred_w && pepi && na9 && g4s)
-                return P.res ? launch_f16x2_ws<3, 1, 1, 1, 4, 9, 1, 1, 3>(P, d, st) : launch_f16x2_ws<3, 1, 1, 1, 4, 9, 1, 0, 3>(P, d, st);
             if (small_co && P.pred_w && pepi && na9)
                 return P.res ? launch_f16x2_ws<3, 1, 1, 1, 4, 9, 1, 1, 1>(P, d, st) : launch_f16x2_ws<3, 1, 1, 1, 4, 9, 1, 0, 1>(P, d, st);
             if (small_co && P.pred_w && pepi)
@@ -2049,16 +1921,6 @@ static int conv3d_dispatch(const v2ce_conv3d_desc *desc, const float *x0, const 
         if (P.sc_w) {
             static const bool na9 = [] { const char *e = getenv("V2CE_NA9"); return !(e && e[0] == '0'); }();
             // (128-channel tiles: both accumulator sets of four fragments and a nine-slot ring do not fit -- 173 spilled registers)
-            // (round 6: the epilogue shared with the producer waves as on the conv with the fused head -- measured SLOWER here, opt-in
-            // with V2CE_PEPI_SC=1: the three 128-channel launches 0.495 -> 0.503 ms, enc0.conv1 0.670 -> 0.713)
-            static const bool pepi_sc = [] { const char *e = getenv("V2CE_PEPI_SC"); return e && e[0] == '1'; }();
-            // (round 6: four lanes per element in the producers' gather, VERDICT r5 #3 (a) -- measured no faster, opt-in with V2CE_G4=1:
-            // the three 128-channel launches 0.482 -> 0.481 ms, enc0.conv1 0.717 -> 0.745, dec3.conv2 + head 0.88 -> 0.89)
-            static const bool g4 = [] { const char *e = getenv("V2CE_G4"); return e && e[0] == '1'; }();
-            if (g4 && d.Cout >= 128) return launch_f16x2_ws<3, 2, 4, 1, 4, 3, 2, 0, 2>(P, d, st);
-            if (g4 && !small_co && na9) return launch_f16x2_ws<3, 2, 2, 1, 2, 9, 2, 0, 2>(P, d, st);
-            if (pepi_sc && d.Cout >= 128 && d.Cout <= 512 && !P.res) return launch_f16x2_ws<3, 2, 4, 1, 4, 3, 2, 0, 1>(P, d, st);
-            if (pepi_sc && !small_co && d.Cout < 128 && na9 && !P.res) return launch_f16x2_ws<3, 2, 2, 1, 2, 9, 2, 0, 1>(P, d, st);
             if (d.Cout >= 128) return launch_f16x2_ws<3, 2, 4, 1, 4, 3, 2, 0>(P, d, st);
             if (!small_co && na9) return launch_f16x2_ws<3, 2, 2, 1, 2, 9, 2, 0>(P, d, st);
             if (!small_co) return launch_f16x2_ws<3, 2, 2, 1, 2, 3, 2, 0>(P, d, st);

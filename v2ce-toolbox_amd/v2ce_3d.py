@@ -427,8 +427,6 @@ class V2ce3d(nn.Module):
         disappears (enc0-3, dec3: ~0.9 ms per 64 frame-pairs)."""
         if self.precision != "f16x2":
             return False
-        if blk.stride_hw == 2 and os.environ.get("V2CE_FOLD_STRIDED", "0") == "1":
-            return False                                   # A/B: the strided blocks' shortcuts as conv2 tails (stride-2 gather)
         return blk.stride_hw == 2 or blk.cout <= 32
 
     def _dec_last_split(self, name, i, blk) -> bool:
