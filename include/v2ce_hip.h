@@ -100,6 +100,14 @@ size_t v2ce_ldati_lds_bytes(double fps, double t0);
  * needs v2ce_ldati_lds_bytes != 0).  Both produce bit-identical output.  Coarse buckets beyond the LDS
  * capacity of a sort workgroup (degenerate ties) are ordered by a dedicated, slower kernel inside the
  * same call; the device status word (v2ce_ldati_status) stays 0 unless an internal limit is hit.
+ * Domain.  Forward relocation: any finite voxel values (negative ones, -0.0, subnormals and integer-typed grids converted to
+ * f32 included) give the reference's events.  Bidirectional relocation: NON-NEGATIVE voxels.  Its single-event times are
+ * bucketed in a key window of one time bin before and one after the event's own bin (per bin c, with vs = 1/fps/9 and
+ * offt_c = (float)(c vs) + (float)t0:  [(int64)(offt_c 1e6) - slack - span,  + 3 span + 2 slack)  microseconds, span =
+ * (int64)(vs 1e6) + 2, slack = 16 + (int64)(8 ulp_us), ulp_us = (|offt_8| + vs) 2^-23 1e6), which holds every tendency of a
+ * non-negative grid (-1 .. 2 bin widths).  A negative voxel can carry a tendency beyond it (bin 8's tendency is y[9]
+ * itself): the call then sets bit 2 (value 4) of the status word and its output must be discarded -- no timestamp is
+ * clamped silently.
  * Options: bidirectional relocation and the pooled slope (a pre-pass writes {k, b} per voxel) run on the
  * two-level path (workspace required); 'random' spreads the timestamps of a bin over a whole second, far
  * beyond the bucket machinery's key range: it takes a generic path (tile pass writing one 64-bit key per
@@ -114,7 +122,9 @@ int v2ce_ldati_emit(const float *vox, int B, int H, int W, double fps, double t0
                     int16_t *x, int16_t *y, int8_t *p, uint8_t *packed, int64_t total_events,
                     int64_t max_segment_events, int64_t max_tile_events, const void *tile_ws,
                     void *workspace, size_t workspace_bytes, v2ce_stream_t stream);
-/* Device address of the status word (int32) inside a workspace used with the same arguments. */
+/* Device address of the status word (int32) inside a workspace used with the same arguments.  Read it after the emit has
+ * finished: 0 = the events are valid; bit 2 (value 4) = a bidirectional call met a tendency outside its key window (negative
+ * voxels: see the domain above); any other value = an internal limit (a segment that could not be ordered). */
 int v2ce_ldati_status(const void *workspace, int B, int H, int W, double fps, double t0,
                       const v2ce_ldati_options *options, int64_t total_events, int64_t max_segment_events,
                       int64_t max_tile_events, const int32_t **status_dev);

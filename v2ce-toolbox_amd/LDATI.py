@@ -93,8 +93,15 @@ class DeviceEvents:
 
     def check(self) -> None:
         """Raise if the device reported a segment it could not order (a coarse bucket beyond the LDS
-        capacity at an fps whose key range the sweep fallback cannot hold).  Synchronises."""
-        if self._status is not None and int(self._status.item()) != 0:
+        capacity at an fps whose key range the sweep fallback cannot hold) or, in a bidirectional call, a
+        tendency outside the key window (status bit 2: negative voxels).  Synchronises."""
+        status = 0 if self._status is None else int(self._status.item())
+        if status & 4 and getattr(self, "_status_message", None) is None:     # (an LDATI call; the samplers have their own word)
+            raise hip.V2ceHipError("LDATI: bidirectional relocation: a tendency left the key window (one time bin before and one "
+                                   "after the event's own bin, which holds every tendency of a non-negative voxel grid); the "
+                                   "voxels hold negative values, for which bidirectional=True is not supported -- the events of "
+                                   "this call are not valid")
+        if status != 0:
             raise hip.V2ceHipError(getattr(self, "_status_message", None) or
                                    "LDATI: a (frame, bin) segment has more equal-time events than the LDS sort "
                                    "holds and the key range of this fps exceeds the sweep kernel's histogram")

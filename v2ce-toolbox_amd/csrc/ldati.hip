@@ -390,6 +390,18 @@ __device__ __forceinline__ int key_of(long long T, long long kbase, int NK) {
     return (int)k;
 }
 
+// Bidirectional relocation (LDATI.py:107-122) gets a key window sized for NON-NEGATIVE voxels (host_scalars): a negative voxel can
+// carry a tendency further out (bin 8's is y[9] itself).  The kernel instances that serve bidirectional calls take their keys
+// from here: the same key, and kStatusKeyWindow in the call's status word when the time lies outside [kbase, kbase + NK) --
+// the clamp would otherwise move the event's timestamp silently.  Forward calls never reach the clamp (the debt stays in
+// (-2e-6, 1), multi-event times in their bin) and keep key_of / multi_key / single_key.
+constexpr unsigned kStatusKeyWindow = 4u;
+__device__ __forceinline__ int key_of_reporting(bool has, long long T, long long kbase, int NK, int *status) {
+    const long long k = T - kbase;
+    if (has && (k < 0 || k >= NK)) atomicOr(reinterpret_cast<unsigned *>(status), kStatusKeyWindow);
+    return key_of(T, kbase, NK);
+}
+
 // the key of a single event: fast form when the wave's tendencies all lie inside the checked range (`fast`: the device
 // verdict, 32-bit times), else the divisions.  Must be called by whole waves (the range test is a wave vote).
 __device__ __forceinline__ unsigned single_key(bool has, float debt, float offt, long long kbase, bool fast, const LdatiParams &P) {
@@ -1128,7 +1140,7 @@ __global__ __launch_bounds__(NT) void ldati_tile_pass_kernel(LdatiParams P) {
         for (unsigned q = tid; q < Ns; q += NT) {
             const uint2 e = SL[q];
             const long long Tq = single_ts(__uint_as_float(e.x), P.fps, P.offt[c]);
-            const unsigned key = (unsigned)key_of(Tq, P.kbase[c], P.NK);
+            const unsigned key = (unsigned)(BIDIR ? key_of_reporting(true, Tq, P.kbase[c], P.NK, P.status) : key_of(Tq, P.kbase[c], P.NK));
             S[q] = (key << 12) | e.y;
             const unsigned w = (unsigned)(((float)q + 0.5f) * invL);
             if (!P.keys) atomicAdd(&hist[__umul24(w >> 1, (unsigned)P.NB) + (key >> P.shift)], 1u << ((w & 1u) * 16u));
@@ -1179,9 +1191,14 @@ __global__ __launch_bounds__(NT) void ldati_tile_pass_kernel(LdatiParams P) {
                         float tt = t[s] + offt_c;
                         tt = tt * 1e6f;
                         int k = (int)tt - kbase_c;
+                        if (BIDIR && (unsigned)s < cnt && (k < 0 || k >= P.NK)) atomicOr(reinterpret_cast<unsigned *>(P.status), kStatusKeyWindow);
                         k = k < 0 ? 0 : k;
                         key[s] = (unsigned)(k >= P.NK ? P.NK - 1 : k);
                     }
+                } else if (BIDIR) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)               // (multi_ts: the 64-bit form of multi_key's time, the same value while P.ts32)
+                        key[s] = (unsigned)key_of_reporting((unsigned)s < cnt, multi_ts(kb.x, kb.y, u[s], P.offt[c], P), P.kbase[c], P.NK, P.status);
                 } else {
 #pragma unroll
                     for (int s = 0; s < 4; ++s)
@@ -1901,7 +1918,7 @@ __global__ __launch_bounds__(256) void ldati_selfcheck_kernel(float VS, float VS
 // record offsets a count pass would have provided are not needed because every tile writes into its own slot of kSparseCap
 // records (`temp` + slot; the (tile, bin) starts go to tile_abs for the bucket sort).  A tile beyond kSparseCap only reports
 // its counts; the host then takes the two-pass path for the call (v2ce_ldati_emit_fused).
-template <bool FUSED>
+template <bool FUSED, bool BIDIR>                        // BIDIR: the instance for bidirectional calls reports keys outside the window
 __global__ __launch_bounds__(kSparseThreads, V2CE_SPARSE_WAVES) void ldati_tile_sparse_kernel(LdatiParams P) {
     constexpr int NT = kSparseThreads, NW = NT / 64, PPT = kTilePix / NT;
     constexpr int HWORDS = NT * 5;                       // 10 cells per thread >= 9 * kMaxNB + 1
@@ -2097,7 +2114,8 @@ __global__ __launch_bounds__(kSparseThreads, V2CE_SPARSE_WAVES) void ldati_tile_
         if ((unsigned)(j * NT) >= Ns) break;                 // uniform: no single left for anybody
         const bool has = (unsigned)(tid + j * NT) < Ns;
         const unsigned c = has ? sl[j].y >> kLocalBits : 0u;
-        const unsigned key = single_key(has, __uint_as_float(sl[j].x), offt_s[c], kbase_s[c], fast_s, P);
+        const unsigned key = BIDIR ? (unsigned)key_of_reporting(has, single_ts(__uint_as_float(sl[j].x), P.fps, offt_s[c]), kbase_s[c], P.NK, P.status)
+                                   : single_key(has, __uint_as_float(sl[j].x), offt_s[c], kbase_s[c], fast_s, P);
         if (has) put((unsigned)(tid + j * NT), c, key, 0u, sl[j].y & (kTilePix - 1));   // a single's record index = its list index
     }
     STAMP(4);
@@ -2131,7 +2149,8 @@ __global__ __launch_bounds__(kSparseThreads, V2CE_SPARSE_WAVES) void ldati_tile_
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
                     if ((unsigned)s < cnt) {
-                        const unsigned key = P.ts32 ? multi_key(mk[j], mb[j], u[s], offt, (int)kb64, P, fast_k0)
+                        const unsigned key = BIDIR ? (unsigned)key_of_reporting(true, multi_ts(mk[j], mb[j], u[s], offt, P), kb64, P.NK, P.status)
+                                           : P.ts32 ? multi_key(mk[j], mb[j], u[s], offt, (int)kb64, P, fast_k0)
                                                     : (unsigned)key_of(multi_ts(mk[j], mb[j], u[s], offt, P), kb64, P.NK);
                         put(i0 + 4u * jb + s, c, key, 1u, local);
                     }
@@ -2920,8 +2939,11 @@ HostScalars host_scalars(double fps, double t0, bool bidir = false, bool random 
     const double ulp_us = top * 1.1920929e-7 * 1e6;      // one f32 ulp of the largest time, in us
     const long long slack = 16 + (long long)(8.0 * ulp_us);
     const long long span = (long long)(vs * 1e6) + 2;
-    // forward relocation: every timestamp lies in its bin.  Bidirectional (LDATI.py:107-122): a single
-    // event's tendency lies in (-1, 2) bin widths (bin 5: bless - debt; bin 8: y[9] < 2 when n == 1).
+    // forward relocation: every timestamp lies in its bin, whatever the (finite) voxel values.  Bidirectional
+    // (LDATI.py:107-122), NON-NEGATIVE voxels: a single event's tendency lies in (-1, 2) bin widths (bin 5: bless - debt;
+    // bin 8: y[9] < 2 when n == 1) -- one bin width before and one after.  With negative voxels no margin holds (bin 8's
+    // tendency is y[9] itself, and n == 1 only bounds y[8] + y[9]): the bidirectional kernel instances report a time
+    // outside the window in the status word (key_of_reporting) and the call is refused (DeviceEvents.check).
     // 'random' (LDATI.py:173-174): the multi-event offsets are raw uniforms in SECONDS.
     const long long before = bidir ? span : 0;
     const long long after = (random ? 1000000 : 0) + (bidir ? span : 0);
@@ -3331,9 +3353,10 @@ extern "C" int v2ce_ldati_count_fused(const float *vox, int B, int H, int W, dou
         hipLaunchKernelGGL(ldati_count_tiles_kernel, dim3(pl.T, B), dim3(kCountThreads), 0, s, vox, H * W, pl.tpp, o.strategy, o.bidir, tc,
                            reinterpret_cast<unsigned long long *>(stats));
     } else {
-    V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ldati_tile_sparse_kernel<true>),
+    auto sparse_kernel = o.bidir ? ldati_tile_sparse_kernel<true, true> : ldati_tile_sparse_kernel<true, false>;
+    V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(sparse_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSparseLds));
-    hipLaunchKernelGGL(ldati_tile_sparse_kernel<true>, dim3(pl.T, B), dim3(kSparseThreads), kSparseLds, s, P);
+    hipLaunchKernelGGL(sparse_kernel, dim3(pl.T, B), dim3(kSparseThreads), kSparseLds, s, P);
     }
     hipLaunchKernelGGL(ldati_tile_scan_kernel, dim3((B + 3) / 4), dim3(256), 0, s, tc, B, pl.T, tile_off, tile_off + (size_t)B * pl.T * 9, pl.Tp,
                        reinterpret_cast<long long *>(seg_offsets), reinterpret_cast<unsigned long long *>(stats));
@@ -3494,9 +3517,10 @@ int emit_impl(const float *vox, int B, int H, int W, double fps, double t0,
         // 2 groups 1.86, 4 groups 1.83, 8 groups 2.21 -- the tile pass needs whole CUs (1024 threads, ~100 KB of LDS), the sort
         // workgroups that slip in between delay its rounds, and each group adds a partial last round.)
         if (P.sparse_cap && !fused) {
-            V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ldati_tile_sparse_kernel<false>),
+            auto sparse_kernel = o.bidir ? ldati_tile_sparse_kernel<false, true> : ldati_tile_sparse_kernel<false, false>;
+            V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(sparse_kernel),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSparseLds));
-            hipLaunchKernelGGL(ldati_tile_sparse_kernel<false>, dim3(pl.T, B), dim3(kSparseThreads), kSparseLds, st, P);
+            hipLaunchKernelGGL(sparse_kernel, dim3(pl.T, B), dim3(kSparseThreads), kSparseLds, st, P);
         }
         if (!fused)
             if (int rc = launch_tile_pass()) return rc;
