@@ -571,6 +571,54 @@ int v2ce_voxelize_batch(const int64_t *ts, const int16_t *x, const int16_t *y, c
 #define V2CE_VOXELIZE_BAD_XY 4
 #define V2CE_VOXELIZE_BAD_RANGE 8
 
+/* The other event -> grid encoders of train/scripts/utils/events_utils.py (csrc/voxelize.hip), P event lists in one
+ * call, laid out as for v2ce_voxelize_batch (SoA columns, offsets int64 [P+1]); every list is encoded on its own.
+ * kinds: mask of V2CE_EVENT_GRIDS_SIGNED | _SPLIT | _STAT; the outputs of a kind that is not requested may be NULL.
+ * All requested kinds are computed from ONE bucketing of the events by (list, pixel).  1 <= bins <= 16.
+ *
+ * SIGNED  events_to_voxel_grid (:70-116): signed_grid [P][bins][H][W] f32.
+ * SPLIT   structured_events_to_voxel_grid (:215-260): split_grid [P][2][bins][H][W] f32, left weights in plane 0,
+ *         right weights in plane 1.
+ *   first / last = the timestamp of the FIRST / LAST row of the list (:87-88, :232-233), deltaT = last - first, 1.0 if
+ *   that is 0 (:89-92); ts = ((bins - 1) * (t - first)) / deltaT in f64 (:94, :239); tis = trunc(ts), dts = ts - tis
+ *   (:101-102); pol = polarity with 0 mapped to -1 (:99, :243); left = pol * (1 - dts) into bin tis, right = pol * dts
+ *   into bin tis + 1, dropped when tis + 1 == bins (:103-112, :247-256).  Every cell adds its lefts in event order,
+ *   then its rights in event order (the two np.add.at calls), each add being acc = (float)((double)acc + v) with v in
+ *   f64: the bytes of the reference while (bins - 1) * (last - first) < 2^53 (the product is formed in f64 here; the
+ *   reference forms it in int64 for structured input and in f64 for an [N, 4] array, which agree below that bound).
+ *   No float atomics; two calls give the same bytes.
+ * STAT    structured_events_to_voxel_stat (:333-358): count, mean, std [P][2][bins][H][W] f64, plane = (polarity == 1)
+ *   (:342).  delta_t = (int) ceil((last - first) / bins), the division in f64 (:334); tb = (t - first) / delta_t,
+ *   tr = (t - first) % delta_t, both 0 when delta_t == 0 (NumPy's integer division by zero) (:336-338).  Count, sum(tr)
+ *   and sum(tr^2) are accumulated as integers (exactly the reference's f64 sums while sum(tr^2) < 2^53), then
+ *   mean = sum / max(count, 1), var = (sumsq - (sum * sum) / max(count, 1)) / max(count - 1, 1), std = sqrt(var) in
+ *   f64, in that order (:354-356); a negative var gives the NaN of the reference (bits 0xfff8000000000000).
+ *
+ * status [P] int32 (device), one word per list:
+ *   V2CE_EVENT_GRIDS_EMPTY          the list is empty (events[-1] raises in the reference)
+ *   V2CE_EVENT_GRIDS_BAD_XY         an x / y outside W x H
+ *   V2CE_EVENT_GRIDS_BAD_TIME       a timestamp outside [first, last] (the reference would index a wrong bin)
+ *   V2CE_EVENT_GRIDS_STAT_TOP_EDGE  STAT only: some tb == bins (last - first is a multiple of bins; IndexError there)
+ *   V2CE_EVENT_GRIDS_STAT_OVERFLOW  STAT only: a cell's sum(tr^2) reached 2^53, where the reference's sum depends on
+ *                                   the order of its adds
+ * A list with one of the first three bits gets zero grids of every kind; one with a STAT bit gets zero count / mean /
+ * std, while its signed and split grids, which do not depend on what the bit reports, are still answered.  The other
+ * lists of the call are unaffected.  Workspace >= v2ce_event_grids_workspace_bytes(...), which returns 0 for arguments
+ * the entry refuses. */
+#define V2CE_EVENT_GRIDS_SIGNED 1
+#define V2CE_EVENT_GRIDS_SPLIT 2
+#define V2CE_EVENT_GRIDS_STAT 4
+#define V2CE_EVENT_GRIDS_EMPTY 1
+#define V2CE_EVENT_GRIDS_BAD_XY 2
+#define V2CE_EVENT_GRIDS_BAD_TIME 4
+#define V2CE_EVENT_GRIDS_STAT_TOP_EDGE 8
+#define V2CE_EVENT_GRIDS_STAT_OVERFLOW 16
+size_t v2ce_event_grids_workspace_bytes(int P, int bins, int H, int W, int64_t n, int kinds);
+int v2ce_event_grids_batch(const int64_t *ts, const int16_t *x, const int16_t *y, const int8_t *p, const int64_t *offsets,
+                           int64_t n, int P, int bins, int H, int W, int kinds, float *signed_grid, float *split_grid,
+                           double *count, double *mean, double *std, int32_t *status, void *workspace,
+                           size_t workspace_bytes, v2ce_stream_t stream);
+
 /* Event-frame video (csrc/event_frames.hip): the array work of write_event_frame_video (v2ce.py:253-269,275-276) on
  * the device.  mode: V2CE_EVENT_FRAMES_POLARITY = keep_polarity=True (channels S0, S1 and a zero plane, float64
  * arithmetic, v2ce.py:255-257), V2CE_EVENT_FRAMES_GREY = keep_polarity=False (S2 three times, float32, v2ce.py:259-260).

@@ -124,6 +124,8 @@ struct VbParams {
     int *idx_a, *idx_b;       // event indices by bucket; idx_b: merge ping-pong
     int *longs, *nlong;       // buckets longer than kVbSmall
     int ncells;
+    int halves = 2;           // 2: buckets (pair, polarity half, pixel); 1: (pair, pixel) -- the event-grid encoders below
+    int skip_mask = -1;       // a pair whose status has one of these bits is not bucketed
 };
 
 __device__ __forceinline__ void pair_span(const VbParams &Q, int pair, long long &lo, long long &hi) {
@@ -189,13 +191,13 @@ __global__ __launch_bounds__(kVbThreads) void vb_status_kernel(VbParams Q) {
 }
 
 __device__ __forceinline__ int vb_bucket(const VbParams &Q, int pair, long long i) {
-    const int half = Q.p[i] <= 0;                                                    // events_utils.py:153, :133-136
-    return ((pair * 2 + half) * Q.H + Q.y[i]) * Q.W + Q.x[i];
+    const int half = Q.halves == 2 && Q.p[i] <= 0;                                   // events_utils.py:153, :133-136
+    return ((pair * Q.halves + half) * Q.H + Q.y[i]) * Q.W + Q.x[i];
 }
 
 __global__ __launch_bounds__(kVbThreads) void vb_count_kernel(VbParams Q) {
     const int pair = blockIdx.y;
-    if (Q.status[pair]) return;
+    if (Q.status[pair] & Q.skip_mask) return;
     long long lo, hi;
     pair_span(Q, pair, lo, hi);
     for (long long i = lo + (long long)blockIdx.x * kVbThreads + threadIdx.x; i < hi; i += (long long)gridDim.x * kVbThreads)
@@ -272,7 +274,7 @@ __global__ __launch_bounds__(kVbThreads) void vb_scan_down_kernel(VbParams Q) {
 
 __global__ __launch_bounds__(kVbThreads) void vb_scatter_kernel(VbParams Q) {
     const int pair = blockIdx.y;
-    if (Q.status[pair]) return;
+    if (Q.status[pair] & Q.skip_mask) return;
     long long lo, hi;
     pair_span(Q, pair, lo, hi);
     for (long long i = lo + (long long)blockIdx.x * kVbThreads + threadIdx.x; i < hi; i += (long long)gridDim.x * kVbThreads) {
@@ -387,10 +389,10 @@ struct VbLayout {
     size_t range, cnt, start, bsum, idx_a, idx_b, longs, nlong, total;
 };
 
-bool vb_layout(int P, int bins, int H, int W, long long n, VbLayout &L) {
-    if (P < 1 || P > 65535 || bins < 2 || bins > kVbMaxBins || H < 1 || W < 1 || H > 32767 || W > 32767) return false;
+bool vb_layout(int P, int bins, int H, int W, long long n, VbLayout &L, int halves = 2, int min_bins = 2) {
+    if (P < 1 || P > 65535 || bins < min_bins || bins > kVbMaxBins || H < 1 || W < 1 || H > 32767 || W > 32767) return false;
     if (n < 0 || n >= (1ll << 31)) return false;
-    L.ncells = 2ll * P * H * W;
+    L.ncells = (long long)halves * P * H * W;
     if (L.ncells >= (1ll << 31) - 1) return false;
     L.nblocks = (L.ncells + 1 + kVbScanBlock - 1) / kVbScanBlock;
     const long long nlong_cap = n / (kVbSmall + 1) + 1;
@@ -442,6 +444,8 @@ extern "C" int v2ce_voxelize_batch(const int64_t *ts, const int16_t *x, const in
     Q.longs = reinterpret_cast<int *>(ws + L.longs);
     Q.nlong = reinterpret_cast<int *>(ws + L.nlong);
     Q.ncells = (int)L.ncells;
+    Q.halves = 2;
+    Q.skip_mask = -1;
     const long long cb = (L.ncells + kVbThreads) / kVbThreads;
     const unsigned cell_blocks = (unsigned)(cb < 8192 ? cb : 8192);
     long long per = (n / P + kVbThreads - 1) / kVbThreads;
@@ -459,6 +463,284 @@ extern "C" int v2ce_voxelize_batch(const int64_t *ts, const int16_t *x, const in
         if (n > kVbSmall) hipLaunchKernelGGL(vb_sort_long_kernel, dim3(512), dim3(kVbThreads), 0, st, Q);
     }
     hipLaunchKernelGGL(vb_walk_kernel, dim3(cell_blocks), dim3(kVbThreads), 0, st, Q);
+    V2CE_HIP_CHECK(hipGetLastError());
+    return V2CE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// v2ce_event_grids_batch: the three other event -> grid encoders of events_utils.py on the bucket pipeline above.
+//
+//   init -> check (coordinates, time window, empty) -> count -> scan -> scatter -> [sort long buckets -> grid walk]
+//        -> [stat walk -> zero the stat grids of flagged lists]
+//
+// * Both polarities of a pixel add into the SAME cells of the signed and the split grid (events_utils.py:107-112,
+//   :251-256), so the buckets are (list, pixel): halves = 1.  All requested kinds read that one bucketing.
+// * Grid walk: one lane per bucket, event order restored as in vb_walk_kernel, the left contributions in event order,
+//   then the right ones: the order of the reference's two np.add.at calls.  Every add is
+//   acc = (float)((double)acc + v) with v in f64, which is what np.add.at does to a float32 array given float64
+//   values.  No float atomics.
+// * Stat walk: one lane per (list, polarity plane, pixel) filters its plane out of the bucket and keeps, per bin, a
+//   32-bit count and 64-bit integer sums of the residue and its square in registers.  Integer sums do not depend on
+//   the order, so the stat grids need no sort; the reference's f64 sums are these integers exactly while sum(tr^2) <
+//   2^53, beyond which the list is flagged instead of answered.  The f64 finalisation follows :354-356 operation by
+//   operation (this file is built without FMA contraction).
+namespace v2ce {
+namespace {
+
+constexpr int kEgFatal = V2CE_EVENT_GRIDS_EMPTY | V2CE_EVENT_GRIDS_BAD_XY | V2CE_EVENT_GRIDS_BAD_TIME;
+constexpr int kEgStatBits = V2CE_EVENT_GRIDS_STAT_TOP_EDGE | V2CE_EVENT_GRIDS_STAT_OVERFLOW;
+constexpr long long kEgTwo53 = 1ll << 53;
+constexpr long long kEgMaxResidue = 94906265ll;     // floor(sqrt(2^53)): a larger residue squares to 2^53 or more
+
+struct EgOut {
+    float *signed_grid, *split_grid;
+    double *count, *mean, *std;
+};
+
+__global__ __launch_bounds__(kVbThreads) void eg_init_kernel(VbParams Q) {
+    const long long stride = (long long)gridDim.x * kVbThreads;
+    for (long long i = (long long)blockIdx.x * kVbThreads + threadIdx.x; i <= Q.ncells; i += stride) {
+        Q.cnt[i] = 0;
+        if (i < Q.P) Q.status[i] = 0;
+        if (i == 0) *Q.nlong = 0;
+    }
+}
+
+// grid (G, P): an empty list (events[-1] raises, :87), coordinates outside H x W, a timestamp outside [first, last]
+__global__ __launch_bounds__(kVbThreads) void eg_check_kernel(VbParams Q) {
+    const int pair = blockIdx.y;
+    long long lo, hi;
+    pair_span(Q, pair, lo, hi);
+    if (hi == lo) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&Q.status[pair], V2CE_EVENT_GRIDS_EMPTY);
+        return;
+    }
+    const long long first = Q.ts[lo], last = Q.ts[hi - 1];                            // :87-88, :232-233, :334
+    int bad = 0;
+    for (long long i = lo + (long long)blockIdx.x * kVbThreads + threadIdx.x; i < hi; i += (long long)gridDim.x * kVbThreads) {
+        const long long t = Q.ts[i];
+        const int xi = Q.x[i], yi = Q.y[i];
+        if (xi < 0 || xi >= Q.W || yi < 0 || yi >= Q.H) bad |= V2CE_EVENT_GRIDS_BAD_XY;
+        if (t < first || t > last) bad |= V2CE_EVENT_GRIDS_BAD_TIME;
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) bad |= __shfl_xor(bad, o);
+    if ((threadIdx.x & (kWave - 1)) == 0 && bad) atomicOr(&Q.status[pair], bad);
+}
+
+// one lane per bucket (list, pixel): lefts in event order, then rights in event order (:107-112, :251-256)
+template <bool SIGNED, bool SPLIT>
+__global__ __launch_bounds__(kVbThreads) void eg_walk_grid_kernel(VbParams Q, EgOut O) {
+    const long long HW = (long long)Q.H * Q.W;
+    for (long long c = (long long)blockIdx.x * kVbThreads + threadIdx.x; c < Q.ncells; c += (long long)gridDim.x * kVbThreads) {
+        const int pair = (int)(c / HW);
+        const long long pix = c % HW;
+        const int c0 = Q.start[c], n = Q.start[c + 1] - c0;
+        int *ix = Q.idx_a + c0;
+        if (n > 1 && n <= kVbSmall)
+            for (int k = 1; k < n; ++k) {
+                const int v = ix[k];
+                int j = k - 1;
+                while (j >= 0 && ix[j] > v) { ix[j + 1] = ix[j]; --j; }
+                ix[j + 1] = v;
+            }
+        float acc[kVbMaxBins], accl[kVbMaxBins], accr[kVbMaxBins];      // signed | split plane 0 | split plane 1
+#pragma unroll
+        for (int q = 0; q < kVbMaxBins; ++q) acc[q] = accl[q] = accr[q] = 0.0f;
+        if (n > 0) {
+            long long lo, hi;
+            pair_span(Q, pair, lo, hi);
+            const long long first = Q.ts[lo], last = Q.ts[hi - 1];
+            const double deltaT = last == first ? 1.0 : (double)(last - first);     // :89-92
+            const double top = (double)(Q.bins - 1);
+            for (int pass = 0; pass < 2; ++pass)
+                for (int k = 0; k < n; ++k) {
+                    const int e = ix[k];
+                    const double ts = (top * (double)(Q.ts[e] - first)) / deltaT;   // :94, :239
+                    const long long tis = (long long)ts;                            // :101 astype(int) truncates
+                    const double dts = ts - (double)tis;                            // :102
+                    const int pe = Q.p[e];
+                    const double pol = pe == 0 ? -1.0 : (double)pe;                 // :99
+                    const double v = pass == 0 ? pol * (1.0 - dts) : pol * dts;     // :103-104
+                    const long long bin = pass == 0 ? tis : tis + 1;                // :106-112: bin >= bins is dropped
+#pragma unroll
+                    for (int q = 0; q < kVbMaxBins; ++q) {
+                        if (SIGNED) acc[q] = bin == q ? (float)((double)acc[q] + v) : acc[q];
+                        if (SPLIT && pass == 0) accl[q] = bin == q ? (float)((double)accl[q] + v) : accl[q];
+                        if (SPLIT && pass == 1) accr[q] = bin == q ? (float)((double)accr[q] + v) : accr[q];
+                    }
+                }
+        }
+#pragma unroll
+        for (int q = 0; q < kVbMaxBins; ++q)
+            if (q < Q.bins) {
+                if (SIGNED) O.signed_grid[((long long)pair * Q.bins + q) * HW + pix] = acc[q];
+                if (SPLIT) {
+                    O.split_grid[((long long)(pair * 2) * Q.bins + q) * HW + pix] = accl[q];
+                    O.split_grid[((long long)(pair * 2 + 1) * Q.bins + q) * HW + pix] = accr[q];
+                }
+            }
+    }
+}
+
+// sqrt(v) rounded to nearest for finite v >= 0, whatever the last bit of the device's sqrt: s is the correctly
+// rounded root iff s * pred(s) < v <= s * succ(s) (the midpoints' squares lie strictly between multiples of the products'
+// grid), and the sign of an fma residual is exact.  One step up or down covers a root that is off by one ulp.
+__device__ __forceinline__ double eg_sqrt_rn(double v) {
+    double s = sqrt(v);
+    if (v > 0.0) {
+        const double up = __longlong_as_double(__double_as_longlong(s) + 1);
+        const double dn = __longlong_as_double(__double_as_longlong(s) - 1);
+        if (fma(-s, up, v) > 0.0) s = up;
+        else if (fma(-s, dn, v) <= 0.0) s = dn;
+    }
+    return s;
+}
+
+// one lane per (list, polarity plane, pixel): integer count, sum(tr), sum(tr^2) per bin, finalised in f64 (:334-356)
+__global__ __launch_bounds__(kVbThreads) void eg_walk_stat_kernel(VbParams Q, EgOut O) {
+    const long long HW = (long long)Q.H * Q.W;
+    const long long total = 2ll * Q.ncells;
+    for (long long g = (long long)blockIdx.x * kVbThreads + threadIdx.x; g < total; g += (long long)gridDim.x * kVbThreads) {
+        const int pair = (int)(g / (2 * HW));
+        const int plane = (int)((g / HW) & 1);
+        const long long pix = g % HW;
+        const long long c = (long long)pair * HW + pix;
+        const int c0 = Q.start[c], n = Q.start[c + 1] - c0;
+        const int *ix = Q.idx_a + c0;
+        unsigned cnt[kVbMaxBins];
+        unsigned long long sum[kVbMaxBins], sq[kVbMaxBins];
+#pragma unroll
+        for (int q = 0; q < kVbMaxBins; ++q) { cnt[q] = 0; sum[q] = 0; sq[q] = 0; }
+        int flag = 0;
+        if (n > 0) {
+            long long lo, hi;
+            pair_span(Q, pair, lo, hi);
+            const long long first = Q.ts[lo], last = Q.ts[hi - 1];
+            const long long delta_t = (long long)ceil((double)(last - first) / (double)Q.bins);      // :334
+            for (int k = 0; k < n; ++k) {
+                const int e = ix[k];
+                if ((Q.p[e] == 1 ? 1 : 0) != plane) continue;                                       // :342
+                const long long t = Q.ts[e] - first;                                                 // :336
+                const long long tb = delta_t ? t / delta_t : 0, tr = delta_t ? t % delta_t : 0;      // :337-338, x // 0 = 0
+                if (tb >= Q.bins) { flag |= V2CE_EVENT_GRIDS_STAT_TOP_EDGE; continue; }
+                if (tr > kEgMaxResidue) { flag |= V2CE_EVENT_GRIDS_STAT_OVERFLOW; continue; }
+                const unsigned long long r = (unsigned long long)tr, r2 = r * r;
+#pragma unroll
+                for (int q = 0; q < kVbMaxBins; ++q)
+                    if (tb == q) {
+                        cnt[q] += 1;
+                        sum[q] += r;
+                        if (sq[q] < (unsigned long long)kEgTwo53) sq[q] += r2;     // sticky at >= 2^53, never wraps
+                    }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kVbMaxBins; ++q)
+            if (q < Q.bins) {
+                if (sq[q] >= (unsigned long long)kEgTwo53) flag |= V2CE_EVENT_GRIDS_STAT_OVERFLOW;
+                const double N = (double)cnt[q], S = (double)sum[q], SS = (double)sq[q];
+                const double d1 = N > 1.0 ? N : 1.0;                               // np.maximum(count, 1)
+                const double d2 = N - 1.0 > 1.0 ? N - 1.0 : 1.0;                   // np.maximum(count - 1, 1)
+                const double mean = S / d1;                                        // :354
+                const double var = (SS - (S * S) / d1) / d2;                       // :355
+                // :356; a negative variance is NaN there: the sign-set quiet NaN that NumPy's sqrt returns on x86-64
+                const double sd = var < 0.0 ? __longlong_as_double((long long)0xfff8000000000000ull) : eg_sqrt_rn(var);
+                const long long o = ((long long)(pair * 2 + plane) * Q.bins + q) * HW + pix;
+                O.count[o] = N;
+                O.mean[o] = mean;
+                O.std[o] = sd;
+            }
+        if (flag) atomicOr(&Q.status[pair], flag);
+    }
+}
+
+// grid (G, P): a list with a stat bit answers zero stat grids (its cells were written before the bit was known)
+__global__ __launch_bounds__(kVbThreads) void eg_zero_stat_kernel(VbParams Q, EgOut O) {
+    const int pair = blockIdx.y;
+    if (!(Q.status[pair] & kEgStatBits)) return;
+    const long long per = 2ll * Q.bins * Q.H * Q.W, base = per * pair;
+    for (long long i = (long long)blockIdx.x * kVbThreads + threadIdx.x; i < per; i += (long long)gridDim.x * kVbThreads) {
+        O.count[base + i] = 0.0;
+        O.mean[base + i] = 0.0;
+        O.std[base + i] = 0.0;
+    }
+}
+
+}  // namespace
+}  // namespace v2ce
+
+extern "C" size_t v2ce_event_grids_workspace_bytes(int P, int bins, int H, int W, int64_t n, int kinds) {
+    VbLayout L;
+    if (kinds < 1 || kinds > 7) return 0;
+    return vb_layout(P, bins, H, W, n, L, 1, 1) ? L.total : 0;
+}
+
+extern "C" int v2ce_event_grids_batch(const int64_t *ts, const int16_t *x, const int16_t *y, const int8_t *p,
+                                      const int64_t *offsets, int64_t n, int P, int bins, int H, int W, int kinds,
+                                      float *signed_grid, float *split_grid, double *count, double *mean, double *std,
+                                      int32_t *status, void *workspace, size_t workspace_bytes, v2ce_stream_t stream) {
+    clear_error();
+    VbLayout L;
+    V2CE_REQUIRE(kinds >= 1 && kinds <= 7, V2CE_ERR_BAD_ARG, "v2ce_event_grids_batch: kinds must be a non-empty mask of "
+                 "V2CE_EVENT_GRIDS_SIGNED | _SPLIT | _STAT, got %d", kinds);
+    V2CE_REQUIRE(vb_layout(P, bins, H, W, n, L, 1, 1), V2CE_ERR_BAD_ARG,
+                 "v2ce_event_grids_batch: needs 1 <= P <= 65535, 1 <= bins <= %d, 1 <= H, W <= 32767, P*H*W < 2^31 - 1 "
+                 "and n in [0, 2^31)", kVbMaxBins);
+    const bool want_signed = kinds & V2CE_EVENT_GRIDS_SIGNED, want_split = kinds & V2CE_EVENT_GRIDS_SPLIT,
+               want_stat = kinds & V2CE_EVENT_GRIDS_STAT;
+    V2CE_REQUIRE(offsets && status && workspace, V2CE_ERR_BAD_ARG, "v2ce_event_grids_batch: null pointer");
+    V2CE_REQUIRE((!want_signed || signed_grid) && (!want_split || split_grid) && (!want_stat || (count && mean && std)),
+                 V2CE_ERR_BAD_ARG, "v2ce_event_grids_batch: null output of a requested kind");
+    V2CE_REQUIRE(n == 0 || (ts && x && y && p), V2CE_ERR_BAD_ARG, "v2ce_event_grids_batch: null event array");
+    V2CE_REQUIRE(workspace_bytes >= L.total, V2CE_ERR_WORKSPACE, "v2ce_event_grids_batch: workspace too small (%zu < %zu)",
+                 workspace_bytes, L.total);
+    hipStream_t st = as_stream(stream);
+    char *ws = static_cast<char *>(workspace);
+    VbParams Q{};
+    Q.ts = ts; Q.x = x; Q.y = y; Q.p = p; Q.off = offsets; Q.n = n;
+    Q.P = P; Q.bins = bins; Q.H = H; Q.W = W; Q.status = status;
+    Q.range = reinterpret_cast<long long *>(ws + L.range);
+    Q.cnt = reinterpret_cast<int *>(ws + L.cnt);
+    Q.start = reinterpret_cast<int *>(ws + L.start);
+    Q.bsum = reinterpret_cast<int *>(ws + L.bsum);
+    Q.idx_a = reinterpret_cast<int *>(ws + L.idx_a);
+    Q.idx_b = reinterpret_cast<int *>(ws + L.idx_b);
+    Q.longs = reinterpret_cast<int *>(ws + L.longs);
+    Q.nlong = reinterpret_cast<int *>(ws + L.nlong);
+    Q.ncells = (int)L.ncells;
+    Q.halves = 1;
+    Q.skip_mask = kEgFatal;
+    EgOut O{signed_grid, split_grid, count, mean, std};
+    const long long cb = (L.ncells + kVbThreads) / kVbThreads;
+    const unsigned cell_blocks = (unsigned)(cb < 8192 ? cb : 8192);
+    const unsigned stat_blocks = (unsigned)(2 * cb < 16384 ? 2 * cb : 16384);
+    long long per = (n / P + kVbThreads - 1) / kVbThreads;
+    const unsigned ge = (unsigned)(per < 1 ? 1 : (per > 1024 ? 1024 : per));
+    hipLaunchKernelGGL(eg_init_kernel, dim3(cell_blocks), dim3(kVbThreads), 0, st, Q);
+    hipLaunchKernelGGL(eg_check_kernel, dim3(ge, P), dim3(kVbThreads), 0, st, Q);
+    if (n > 0) hipLaunchKernelGGL(vb_count_kernel, dim3(ge, P), dim3(kVbThreads), 0, st, Q);
+    hipLaunchKernelGGL(vb_scan_reduce_kernel, dim3((unsigned)L.nblocks), dim3(kVbThreads), 0, st, Q);
+    hipLaunchKernelGGL(vb_scan_top_kernel, dim3(1), dim3(1024), 0, st, Q, (int)L.nblocks);
+    hipLaunchKernelGGL(vb_scan_down_kernel, dim3((unsigned)L.nblocks), dim3(kVbThreads), 0, st, Q);
+    if (n > 0) hipLaunchKernelGGL(vb_scatter_kernel, dim3(ge, P), dim3(kVbThreads), 0, st, Q);
+    if (want_signed || want_split) {                            // only the float grids depend on the event order
+        if (n > 0) {
+            hipLaunchKernelGGL(vb_classify_kernel, dim3(cell_blocks), dim3(kVbThreads), 0, st, Q);
+            if (n > kVbSmall) hipLaunchKernelGGL(vb_sort_long_kernel, dim3(512), dim3(kVbThreads), 0, st, Q);
+        }
+        if (want_signed && want_split)
+            hipLaunchKernelGGL((eg_walk_grid_kernel<true, true>), dim3(cell_blocks), dim3(kVbThreads), 0, st, Q, O);
+        else if (want_signed)
+            hipLaunchKernelGGL((eg_walk_grid_kernel<true, false>), dim3(cell_blocks), dim3(kVbThreads), 0, st, Q, O);
+        else
+            hipLaunchKernelGGL((eg_walk_grid_kernel<false, true>), dim3(cell_blocks), dim3(kVbThreads), 0, st, Q, O);
+    }
+    if (want_stat) {
+        const long long zb = (2ll * bins * H * W + kVbThreads - 1) / kVbThreads;
+        hipLaunchKernelGGL(eg_walk_stat_kernel, dim3(stat_blocks), dim3(kVbThreads), 0, st, Q, O);
+        hipLaunchKernelGGL(eg_zero_stat_kernel, dim3((unsigned)(zb < 256 ? zb : 256), P), dim3(kVbThreads), 0, st, Q, O);
+    }
     V2CE_HIP_CHECK(hipGetLastError());
     return V2CE_OK;
 }

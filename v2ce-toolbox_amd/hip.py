@@ -37,6 +37,7 @@ EXPORTS = [
     "v2ce_tsdiff_workspace_bytes", "v2ce_tsdiff",
     "v2ce_voxmetrics_workspace_bytes", "v2ce_voxmetrics", "v2ce_voxelize_batch_workspace_bytes", "v2ce_voxelize_batch",
     "v2ce_event_frames_hist_bytes", "v2ce_event_frames_sums", "v2ce_event_frames_refine", "v2ce_event_frames_render",
+    "v2ce_event_grids_workspace_bytes", "v2ce_event_grids_batch",
 ]
 
 
@@ -90,6 +91,10 @@ class VoxMetricsStats(ctypes.Structure):
 
 
 VOXELIZE_EMPTY, VOXELIZE_SINGLE_TIMESTAMP, VOXELIZE_BAD_XY, VOXELIZE_BAD_RANGE = 1, 2, 4, 8
+
+EVENT_GRIDS_SIGNED, EVENT_GRIDS_SPLIT, EVENT_GRIDS_STAT = 1, 2, 4
+(EVENT_GRIDS_EMPTY, EVENT_GRIDS_BAD_XY, EVENT_GRIDS_BAD_TIME, EVENT_GRIDS_STAT_TOP_EDGE,
+ EVENT_GRIDS_STAT_OVERFLOW) = 1, 2, 4, 8, 16
 
 EVENT_FRAMES_POLARITY, EVENT_FRAMES_GREY = 0, 1
 EVENT_FRAMES_LEVEL0_BINS, EVENT_FRAMES_REFINE_BINS = 2048, 1024
@@ -236,6 +241,10 @@ def lib() -> ctypes.CDLL:
     L.v2ce_voxelize_batch_workspace_bytes.restype = sz
     L.v2ce_voxelize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
     L.v2ce_voxelize_batch.restype = ctypes.c_int
+    L.v2ce_event_grids_workspace_bytes.argtypes = [i32, i32, i32, i32, i64, i32]
+    L.v2ce_event_grids_workspace_bytes.restype = sz
+    L.v2ce_event_grids_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.v2ce_event_grids_batch.restype = ctypes.c_int
     L.v2ce_event_frames_hist_bytes.argtypes = [i32]
     L.v2ce_event_frames_hist_bytes.restype = sz
     L.v2ce_event_frames_sums.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
