@@ -116,12 +116,10 @@ WALK_CASES = [
     # -- fused 1x1x1 head (shared epilogue, PEPI)
     Case(f"{WS}<3,1,1,1,4,9,1,1,1>", "pred", 3, 8, 32, 32, 101, 163, res=True),
     Case(f"{WS}<3,1,1,1,4,9,1,0,1>", "pred", 3, 8, 32, 32, 101, 163),
-    # -- folded 1x1x1 tail (FUSE 3), and behind the fused head with a low-resolution residual (FUSE 4)
+    # -- folded 1x1x1 tail (FUSE 3)
     Case(f"{WS}<3,1,1,2,4,3,3,0,0>", "tail", 3, 8, 32, 96, 91, 91, tc=32),
     Case(f"{WS}<3,1,2,2,4,3,3,0,0>", "tail", 3, 8, 32, 384, 67, 67, tc=64),
     Case(f"{WS}<3,1,2,2,3,3,3,0,0>", "tail", 3, 8, 32, 384, 51, 51, tc=64),
-    Case(f"{WS}<3,1,1,1,4,9,4,1,0>", "tail_pred", 3, 8, 32, 32, 101, 163, res=True, tc=32),
-    Case(f"{WS}<3,1,1,1,4,9,4,0,0>", "tail_pred", 3, 8, 32, 32, 101, 163, tc=32),
     # -- Winograd-T (pairs of time steps; odd T)
     Case("conv3d_wt_kernel<2,4,0,0>", "wt", 3, 5, 32, 320, 45, 49),
     Case("conv3d_wt_kernel<2,4,1,0>", "wt", 3, 7, 32, 192, 53, 55, res=True),
@@ -157,7 +155,7 @@ def _variant(c):
         return hip.conv_wt_variant(d, (3 if c.res else 2) if c.kind == "wt_tail" else int(c.res))
     if c.kind.startswith("up"):
         return hip.conv_up2_variant(d, c.kind == "up_sc")
-    fuse = {"ws": 0, "sc": 2, "pred": 1, "tail": 3, "tail_pred": 8}[c.kind]
+    fuse = {"ws": 0, "sc": 2, "pred": 1, "tail": 3}[c.kind]
     return hip.conv_variant(d, False, fuse + (4 if c.res else 0))
 
 
@@ -208,7 +206,7 @@ def _inputs(c):
     I["scale"] = torch.rand(Cout, generator=g) + 0.5
     I["shift"] = 0.3 * torch.randn(Cout, generator=g) * 2.0 ** SCALE_EXP[0]
     if c.res:
-        lo = c.kind in ("tail_pred", "wt_tail")          # a low-resolution residual read at (h >> 1, w >> 1)
+        lo = c.kind == "wt_tail"                         # a low-resolution residual read at (h >> 1, w >> 1)
         I["res"] = torch.randn(B, Cout, T, *(((Ho + 1) // 2, (Wo + 1) // 2) if lo else (Ho, Wo)), generator=g) * k
     if c.kind in ("sc", "up_sc"):
         I["wd"] = torch.randn(Cout, cin, 1, 1, 1, generator=g) * (1.0 / cin) ** 0.5
@@ -217,7 +215,7 @@ def _inputs(c):
     if c.tc:
         I["tx"] = torch.randn(B, c.tc, T, Ho, Wo, generator=g) * k
         I["wd"] = torch.randn(Cout, c.tc, 1, 1, 1, generator=g) * (1.0 / c.tc) ** 0.5
-    if c.kind in ("pred", "tail_pred"):
+    if c.kind == "pred":
         I["wp"] = torch.randn(HEAD_CH, 32, generator=g) * 0.2
         I["bp"] = torch.randn(HEAD_CH, generator=g) * 0.1 * 2.0 ** SCALE_EXP[0]
     return I
@@ -247,11 +245,11 @@ def reference(c, I, pos):
     if c.res:
         b, t, h, ww = pos
         r = I["res"].double()
-        y = y + (r[b, :, t, h >> 1, ww >> 1] if c.kind in ("tail_pred", "wt_tail") else r[b, :, t, h, ww])
+        y = y + (r[b, :, t, h >> 1, ww >> 1] if c.kind == "wt_tail" else r[b, :, t, h, ww])
     out = {"y": y if c.kind == "up_part" else torch.relu(y)}
     if c.kind in ("sc", "up_sc"):
         out["y2"] = conv_at(x, I["wd"], c.s, pos) * col(I["scale2"]) + col(I["shift2"])
-    if c.kind in ("pred", "tail_pred"):
+    if c.kind == "pred":
         out["y"] = torch.relu(out["y"] @ I["wp"].double().t() + col(I["bp"]))
     return out
 
@@ -348,14 +346,13 @@ def launch(c, I):
             wq = V2ce3d._pack(m, cu(I["w"]), None, buf, split=True)
         else:
             wq = V2ce3d._pack(m, cu(I["w"]), split=True)
-        pred = c.kind in ("pred", "tail_pred")
+        pred = c.kind == "pred"
         kw = dict(split=True, dense_out=not pred)
-        lo = c.kind in ("tail_pred", "wt_tail")
         if c.res:
-            kw["residual"] = _dev(I["res"], pitch=pred and not lo)
-            kw["residual_up"] = lo
+            kw["residual"] = _dev(I["res"], pitch=pred)
+            kw["residual_up"] = c.kind == "wt_tail"
         if c.tc:
-            kw["tail"] = (_dev(I["tx"], pitch=pred), None, None, 1, V2ce3d._pack(m, cu(I["wd"]), split=True))
+            kw["tail"] = (_dev(I["tx"]), None, None, 1, V2ce3d._pack(m, cu(I["wd"]), split=True))
         if c.kind == "sc":
             kw["sc"] = (V2ce3d._pack(m, cu(I["wd"]), split=True), cu(I["scale2"]), cu(I["shift2"]))
         if pred:
@@ -411,7 +408,7 @@ def test_walk_vs_f64(case, capfd, monkeypatch):
     slot = got["slot"]
     for b in range(B):
         assert np.isfinite(slot[b, 1]) and slot[b, 1] > 0, (b, slot[b])
-        if case.kind not in ("pred", "tail_pred"):
+        if case.kind != "pred":
             ymax = float(np.abs(got["y"][b]).max())
             assert abs(float(slot[b, 0]) - ymax) <= 1e-6 * ymax, (b, float(slot[b, 0]), ymax)
     if case.kind.startswith("wt"):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of a conv switch (round 6): parity tests, then the e2e bench both ways on one box.
-#   VAR=V2CE_PEPI (default: the last decoder conv's epilogue shared with the producer waves), V2CE_NA9,
+#   VAR=V2CE_PEPI (default: the last decoder conv's epilogue shared with the producer waves),
 #   V2CE_LDATI_STREAM ...; MODES="1 0 1 0"
 TAG=${1:-pepi}
 VAR=${VAR:-V2CE_PEPI}
@@ -14,5 +14,5 @@ for mode in ${MODES:-1 0 1 0}; do
   grep "^{" $OUT/e2e_$mode.log | python3 -c "
 import sys,json; j=json.loads(sys.stdin.readline()); print('$VAR=$mode', 'ms/step', round(j['ms_per_step'],4), 'value', round(j['value'],1))
 for k,v in j['kernels'].items():
-    if ',9,1,' in k or ',3,1,' in k or 'ws_kernel<3,2,' in k or 'up_kernel<1,1,4' in k: print('    %.3f ms x%d  %s' % (v['avg_ms'], v['launches'], k))"
+    if ',9,1,' in k or 'ws_kernel<3,2,' in k or 'up_kernel<1,1,4' in k: print('    %.3f ms x%d  %s' % (v['avg_ms'], v['launches'], k))"
 done

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
-"""Upper bound of what the spectral-norm side stream costs the convolutions it overlaps: time the forward
-pass with the per-call power iteration + weight re-pack enabled, and with it skipped (weights of the
-first call reused).  Diagnostic only."""
+"""What the in-line spectral-norm update costs a forward pass: time the forward pass with the per-call power
+iteration enabled, and with it skipped (weights of the first call reused); then the update alone.  Diagnostic only."""
 import os
 import sys
 import time
@@ -31,9 +30,9 @@ def timed(n=8):
 
 
 a = timed()
-V2ce3d._launch_sn = lambda self: None
+m._sn_all = lambda: None
 b = timed()
-print(f"forward with SN stream {a:.3f} ms, without {b:.3f} ms")
+print(f"forward with the spectral-norm update {a:.3f} ms, without {b:.3f} ms")
 
 # the spectral-norm work alone (12 power iterations + re-packs, nothing else on the GPU)
 m2 = V2ce3d()

@@ -25,6 +25,7 @@
 // through row/column index maps, the rest from the skip tensor -- neither the upsampled tensor nor
 // the concatenation is ever written to HBM.
 #include "conv3d_dev.h"
+#include "conv3d_host.h"
 
 #include <cstdlib>
 #include <map>
@@ -354,8 +355,6 @@ __global__ __launch_bounds__(256, MW) void conv3d_kernel(ConvParams P) {
 // FUSE: 0 = plain, 1 = fused 1x1x1 head (pred_epilogue), 2 = fused 1x1x1 shortcut (second accumulator set),
 //       3 = folded 1x1x1 tail: a residual block's shortcut as P.tCG more K chunks of the SAME accumulators (conv2 of the
 //           block: relu(s2 (W2 * t + Wd' * x) + shift), Wd' = Wd sd / s2 folded on the host; no shortcut tensor at all)
-//       4 = 3 + 1 (round 6): the folded tail AND the fused head -- conv2 of the last decoder block with its shortcut split by source:
-//           the skip channels ride as the tail, the upsampled channels' share arrives as a low-resolution residual (P.res_up)
 // RES: residual known at compile time (0 = none, 1 = present) or checked at run time (2), see conv_epilogue
 // OPT 1, "PEPI" (round 6): the tile's epilogue is SHARED between the roles.  The 32-channel tile with the fused head has two chunks
 //       of 324 MFMAs per wave and an epilogue (residual, scale / shift, ReLU, the head's MFMAs, 20 planar channels of stores) that
@@ -381,7 +380,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
     constexpr int kKeepFr = PEPI ? V2CE_PEPI_KEEP : PO_FR, kDumpFr = PO_FR - kKeepFr;
     constexpr int kDumpSets = 1;                             // accumulator sets of a fragment that travel
     constexpr int kDumpWave = kDumpFr * kDumpSets * 4 * 64;  // f32x4 per consumer wave in the accumulator dump (PEPI)
-    int chs_ = (FUSE == 3 || FUSE == 4) ? P.tCHS : (P.plane + 63) & ~63;
+    int chs_ = FUSE == 3 ? P.tCHS : (P.plane + 63) & ~63;
     if (PEPI && chs_ < kDumpWave) chs_ = kDumpWave;          // a pieces buffer (4 chs x 16 B) holds the four waves' dumps
     const int chs = chs_;
     f16x8 *pieces = reinterpret_cast<f16x8 *>(conv_smem);                      // [2][4][chs] x 16 B
@@ -441,7 +440,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
         return am;
     };
     auto scale_of = [&](int b) -> float { return P.x0_absmax ? pow2_prescale(amax_of(b)) : kActScale; };
-    constexpr bool TAIL = FUSE == 3 || FUSE == 4;
+    constexpr bool TAIL = FUSE == 3;
     static_assert(!TAIL || KS == 3, "the folded tail rides behind a 3x3x3 conv");
     const int CGT = TAIL ? CG + P.tSC : CG;                  // barriers (chunks / tail super-chunks) per tile
     auto tamax_of = [&](int b) -> float {                    // the same for the tail's input
@@ -1183,28 +1182,9 @@ __global__ __launch_bounds__(512, 1) void conv3d_f16x2_ws_kernel(ConvParams P) {
                 ACC_T(tc_own, to);
             }
         } else
-        if constexpr (FUSE == 1 || FUSE == 4) {                 // 32-channel conv with the fused 1x1x1 head
+        if constexpr (FUSE == 1) {                              // 32-channel conv with the fused 1x1x1 head
             static_assert(KS == 3 && S == 1 && WCO == 1 && CO_FR == 1, "the fused head rides on a 32-channel tile");
-            if constexpr (FUSE == 4 && RES == 1) {
-                int rp[PO_FR];                                  // the low-resolution residual's offsets (conv_epilogue, rpoff)
-#pragma unroll
-                for (int f = 0; f < PO_FR; ++f) {
-                    const int m = (wpo * PO_FR + f) * 32 + l32;
-                    rp[f] = -1;
-                    if (m < P.n_pos) {
-                        const int tt = m / (P.TH * P.TW);
-                        const int rem = m - tt * (P.TH * P.TW);
-                        const int th = rem / P.TW;
-                        const int tw = rem - th * P.TW;
-                        const int t = T.t0 + tt, h = T.h0 + th, w = T.w0 + tw;
-                        if (t < P.T && h < P.Hout && w < P.Wout)
-                            rp[f] = 4 * ((t * P.Cout) * (P.rH * P.rWp)) + 64 * ((h >> 1) * P.rWp + (w >> 1));
-                    }
-                }
-                conv_epilogue<CO_FR, PO_FR, true, true, RES, true>(P, acc, poff, co0, half, T.b, out_inv_scale, &rp);
-            } else {
-                conv_epilogue<CO_FR, PO_FR, true, true, RES, true>(P, acc, poff, co0, half, T.b, out_inv_scale);
-            }
+            conv_epilogue<CO_FR, PO_FR, true, true, RES, true>(P, acc, poff, co0, half, T.b, out_inv_scale);
             pred_epilogue<PO_FR>(P, acc, wpo * PO_FR * 32, lane, T.b, T.t0, T.h0, T.w0);
         } else {
             conv_epilogue<CO_FR, PO_FR, true, false, RES, true>(P, acc, poff, co0, half, T.b, out_inv_scale);   // Cout need not fill the last channel tile
@@ -1480,9 +1460,6 @@ Tile measured_box(int T, int Ho, int Wo, int s, int pos_tile) {
     return Tile{0, 0, 0};
 }
 
-thread_local char *g_name_out = nullptr;   // non-null: report the variant instead of launching
-thread_local size_t g_name_cap = 0;
-
 double tile_efficiency(int T, int Ho, int Wo, int ks, int s, int pos_tile, int max_plane) {
     const Tile t = choose_tile(T, Ho, Wo, ks, s, pos_tile, max_plane);
     const long long ntiles = (long long)((T + t.tt - 1) / t.tt) * ((Ho + t.th - 1) / t.th) * ((Wo + t.tw - 1) / t.tw);
@@ -1584,7 +1561,7 @@ int launch_f16x2_ws(ConvParams P, const v2ce_conv3d_desc &d, hipStream_t stream)
     P.per_xcd = (P.n_spatial + 7) / 8;
     const long long blocks = (long long)8 * P.per_xcd * P.n_co_tiles;
     int chs = (P.plane + 63) & ~63;
-    if (FUSE == 3 || FUSE == 4) {
+    if (FUSE == 3) {
         // tail super-chunks: as many channel groups per barrier as the producers' 5 x 256 element slots (= 160 KB of pieces) hold
         P.tNPP = (P.n_pos + 63) & ~63;
         const int tch = 1280 / P.tNPP;
@@ -1607,17 +1584,9 @@ int launch_f16x2_ws(ConvParams P, const v2ce_conv3d_desc &d, hipStream_t stream)
     V2CE_HIP_CHECK(hipMalloc(&P.stamps, (size_t)blocks * 32 * sizeof(unsigned long long)));    // (PEPI: accumulators behind the first grid * 16)
     V2CE_HIP_CHECK(hipMemset(P.stamps, 0, (size_t)blocks * 32 * sizeof(unsigned long long)));
 #endif
-    // persistent: one workgroup per CU walks the virtual blocks (a multiple of 8 keeps tiles on their XCD)
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            n = 256;
-        return n < 8 ? 8 : (n / 8) * 8;
-    }();
+    // persistent: one workgroup per CU walks the virtual blocks
     P.total_blocks = (int)blocks;
-    // (measured in the network, same box: 2200 vs 2143 frame-pairs/s against one tile per workgroup)
-    const unsigned grid = (unsigned)(blocks > n_cu ? n_cu : blocks);
+    const unsigned grid = persistent_grid(blocks);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, P);
     V2CE_HIP_CHECK(hipGetLastError());
 #ifdef V2CE_STAMP
@@ -1641,7 +1610,7 @@ int launch_f16x2_ws(ConvParams P, const v2ce_conv3d_desc &d, hipStream_t stream)
                 KS, S, WCO, CO_FR, PO_FR, NA, P.Cin / 16, P.plane, blocks, med(0, 0, 1), med(0, 1, 2), med(0, 2, 3), med(0, 3, 4), med(0, 0, 4),
                 med(1, 0, 1), med(1, 1, 2), med(1, 2, 3), med(1, 3, 4), med(1, 4, 5), med(1, 0, 6));
         if (PEPI) {
-            const unsigned grid_ = (unsigned)(blocks > n_cu ? n_cu : blocks);
+            const unsigned grid_ = grid;
             auto acc = [&](int role, int k) {
                 std::vector<long long> v;
                 for (unsigned b = 0; b < grid_; ++b) {
@@ -1744,7 +1713,7 @@ static int conv3d_dispatch(const v2ce_conv3d_desc *desc, const float *x0, const 
                            const float *sc_scale = nullptr, const float *sc_shift = nullptr, float *sc_y = nullptr,
                            const v2ce_conv3d_desc *tail = nullptr, const float *tx0 = nullptr, const float *tx1 = nullptr,
                            const int32_t *thmap = nullptr, const int32_t *twmap = nullptr,
-                           const float *tx0_absmax = nullptr, const float *tx1_absmax = nullptr, int res_h = 0, int res_wp = 0) {
+                           const float *tx0_absmax = nullptr, const float *tx1_absmax = nullptr) {
     clear_error();
     V2CE_REQUIRE(desc && (g_name_out || (x0 && w_packed && scale && shift && (y || pred_w))), V2CE_ERR_BAD_ARG,
                  "v2ce_conv3d_fwd: null pointer");
@@ -1792,19 +1761,10 @@ static int conv3d_dispatch(const v2ce_conv3d_desc *desc, const float *x0, const 
     P.sc_w = static_cast<const _Float16 *>(sc_w); P.sc_scale = sc_scale; P.sc_shift = sc_shift; P.sc_y = sc_y;
     if (tail) {
         const v2ce_conv3d_desc &t = *tail;
-        // (round 6, v2ce_conv3d_fwd_tail_pred: the 32-channel conv with the fused head takes a tail too, and with it a low-resolution
-        // residual -- the last decoder block's shortcut split by source)
-        const bool tail_pred = pred_w && d.Cout == 32 && (!residual || res_h > 0);
         V2CE_REQUIRE(d.precision == V2CE_PRECISION_F16X2 && d.ksize == 3 && d.stride_hw == 1 && sc_w && !sc_y &&
-                     (tail_pred || (d.Cout >= 64 && !pred_w && !residual)), V2CE_ERR_UNSUPPORTED,
+                     d.Cout >= 64 && !pred_w && !residual, V2CE_ERR_UNSUPPORTED,
                      "v2ce_conv3d_fwd_tail: the folded tail rides behind a split-half 3x3x3 stride-1 conv with >= 64 output channels, "
-                     "no residual and no fused head -- or behind the 32-channel conv with the fused head (v2ce_conv3d_fwd_tail_pred)");
-        if (residual && res_h > 0) {
-            V2CE_REQUIRE(res_h == (d.Hout + 1) / 2 && res_wp >= (d.Wout + 1) / 2, V2CE_ERR_BAD_ARG,
-                         "v2ce_conv3d_fwd_tail_pred: an upsampled residual has ceil(Hout / 2) rows of at least ceil(Wout / 2) columns");
-            V2CE_REQUIRE((long long)d.T * d.Cout * res_h * res_wp < (1ll << 29), V2CE_ERR_UNSUPPORTED, "v2ce_conv3d_fwd_tail_pred: residual too large");
-            P.res_up = 1; P.rH = res_h; P.rWp = res_wp;
-        }
+                     "no residual and no fused head");
         V2CE_REQUIRE(t.ksize == 1 && (t.stride_hw == 1 || t.stride_hw == 2) && t.layout == V2CE_LAYOUT_C16 && t.B == d.B && t.T == d.T &&
                      t.Cout == d.Cout && t.Hout == d.Hout && t.Wout == d.Wout && t.C0 > 0 && t.C0 % 16 == 0 && t.C1 >= 0 &&
                      t.C1 % 16 == 0 && t.Hout == (t.Hin - 1) / t.stride_hw + 1 && t.Wout == (t.Win - 1) / t.stride_hw + 1,
@@ -1866,42 +1826,12 @@ static int conv3d_dispatch(const v2ce_conv3d_desc *desc, const float *x0, const 
             // form (RES 1) pays on the 32-channel tiles only (+3 %; the two-fragment-row tiles lose 6-12 % to its
             // registers), the others keep the run-time form
 #define V2CE_WS_RES(R_, ...) (P.res ? launch_f16x2_ws<__VA_ARGS__, R_>(P, d, st) : launch_f16x2_ws<__VA_ARGS__, 0>(P, d, st))
-            // (one 32-channel fragment row per wave: 12 MFMAs per tap -- a ring of nine taps covers the weight loads' L2 latency
-            // where three do not; V2CE_NA9=0: the three-slot ring)
-            static const bool na9 = [] { const char *e = getenv("V2CE_NA9"); return !(e && e[0] == '0'); }();
-            if (small_co && P.pred_w && tail)              // the fused head behind a conv with a folded tail (round 6)
-                return P.res ? launch_f16x2_ws<3, 1, 1, 1, 4, 9, 4, 1>(P, d, st) : launch_f16x2_ws<3, 1, 1, 1, 4, 9, 4, 0>(P, d, st);
-            // (round 6: its epilogue on the producer waves; V2CE_PEPI=0: the consumers' own)
-            static const bool pepi = [] { const char *e = getenv("V2CE_PEPI"); return !(e && e[0] == '0'); }();
-            // (nine ring slots: the consumers' path has the registers -- the 229 of the kernel are the producers' -- 0.94 -> 0.91 ms)
-            if (small_co && P.pred_w && pepi && na9)
-                return P.res ? launch_f16x2_ws<3, 1, 1, 1, 4, 9, 1, 1, 1>(P, d, st) : launch_f16x2_ws<3, 1, 1, 1, 4, 9, 1, 0, 1>(P, d, st);
-            if (small_co && P.pred_w && pepi)
-                return P.res ? launch_f16x2_ws<3, 1, 1, 1, 4, 3, 1, 1, 1>(P, d, st) : launch_f16x2_ws<3, 1, 1, 1, 4, 3, 1, 0, 1>(P, d, st);
-            if (small_co && P.pred_w && na9) return V2CE_WS_RES(1, 3, 1, 1, 1, 4, 9, 1);
-            if (small_co && P.pred_w) return V2CE_WS_RES(1, 3, 1, 1, 1, 4, 3, 1);
-            if (small_co && P.sc_w) return launch_f16x2_ws<3, 1, 1, 1, 4, 3, 2, 0>(P, d, st);
-            if (small_co) return V2CE_WS_RES(1, 3, 1, 1, 1, 4, 3, 0);
-            if (tail) {                                   // folded shortcut: no residual by construction
-                if (d.Cout >= 128) {
-                    auto cost = [&](int pos_tile) {
-                        const Tile t = choose_tile(d.T, d.Hout, d.Wout, 3, 1, pos_tile, 1280);
-                        const long long nsp = (long long)d.B * ((d.T + t.tt - 1) / t.tt) * ((d.Hout + t.th - 1) / t.th) *
-                                              ((d.Wout + t.tw - 1) / t.tw);
-                        const long long blocks = 8 * ((nsp + 7) / 8) * ((d.Cout + 127) / 128);
-                        return ((blocks + 255) / 256) * pos_tile;
-                    };
-                    const bool po3 = d.tile_t > 0 ? d.tile_t * d.tile_h * d.tile_w <= 192 : cost(192) < cost(256);
-                    if (po3) return launch_f16x2_ws<3, 1, 2, 2, 3, 3, 3, 0>(P, d, st);
-                    return launch_f16x2_ws<3, 1, 2, 2, 4, 3, 3, 0>(P, d, st);
-                }
-                return launch_f16x2_ws<3, 1, 1, 2, 4, 3, 3, 0>(P, d, st);
-            }
-            if (d.Cout >= 128) {
-                // 256- or 192-position boxes (4 or 3 position fragments per wave): whichever needs fewer
-                // (workgroup rounds x box size).  17x22 planes: (16,2,8) boxes use 87 % of the MFMA lanes and
-                // 448 virtual blocks are 1.75 rounds over 256 CUs; (1,17,11) boxes use 97 % and make exactly 2
-                // rounds of 3/4 the size: 25 % less MFMA time on the five 512-channel launches
+            // >= 128 output channels: 256- or 192-position boxes (4 or 3 position fragments per wave), whichever needs fewer
+            // (workgroup rounds x box size).  17x22 planes: (16,2,8) boxes use 87 % of the MFMA lanes and
+            // 448 virtual blocks are 1.75 rounds over 256 CUs; (1,17,11) boxes use 97 % and make exactly 2
+            // rounds of 3/4 the size: 25 % less MFMA time on the five 512-channel launches
+            auto po3 = [&]() -> bool {
+                if (d.tile_t > 0) return d.tile_t * d.tile_h * d.tile_w <= 192;
                 auto cost = [&](int pos_tile) {
                     const Tile t = choose_tile(d.T, d.Hout, d.Wout, 3, 1, pos_tile, 1280);
                     const long long nsp = (long long)d.B * ((d.T + t.tt - 1) / t.tt) * ((d.Hout + t.th - 1) / t.th) *
@@ -1909,8 +1839,26 @@ static int conv3d_dispatch(const v2ce_conv3d_desc *desc, const float *x0, const 
                     const long long blocks = 8 * ((nsp + 7) / 8) * ((d.Cout + 127) / 128);
                     return ((blocks + 255) / 256) * pos_tile;
                 };
-                const bool po3 = d.tile_t > 0 ? d.tile_t * d.tile_h * d.tile_w <= 192 : cost(192) < cost(256);
-                if (po3) return V2CE_WS_RES(2, 3, 1, 2, 2, 3, 3, 0);
+                return cost(192) < cost(256);
+            };
+            // the fused head, one 32-channel fragment row per wave: 12 MFMAs per tap -- a ring of nine taps covers the weight loads'
+            // L2 latency where three do not (0.94 -> 0.91 ms; the consumers' path has the registers, the 229 of the kernel are
+            // the producers').  Its epilogue runs on the producer waves (round 6); V2CE_PEPI=0: the consumers' own
+            static const bool pepi = [] { const char *e = getenv("V2CE_PEPI"); return !(e && e[0] == '0'); }();
+            if (small_co && P.pred_w && pepi)
+                return P.res ? launch_f16x2_ws<3, 1, 1, 1, 4, 9, 1, 1, 1>(P, d, st) : launch_f16x2_ws<3, 1, 1, 1, 4, 9, 1, 0, 1>(P, d, st);
+            if (small_co && P.pred_w) return V2CE_WS_RES(1, 3, 1, 1, 1, 4, 9, 1);
+            if (small_co && P.sc_w) return launch_f16x2_ws<3, 1, 1, 1, 4, 3, 2, 0>(P, d, st);
+            if (small_co) return V2CE_WS_RES(1, 3, 1, 1, 1, 4, 3, 0);
+            if (tail) {                                   // folded shortcut: no residual by construction
+                if (d.Cout >= 128) {
+                    if (po3()) return launch_f16x2_ws<3, 1, 2, 2, 3, 3, 3, 0>(P, d, st);
+                    return launch_f16x2_ws<3, 1, 2, 2, 4, 3, 3, 0>(P, d, st);
+                }
+                return launch_f16x2_ws<3, 1, 1, 2, 4, 3, 3, 0>(P, d, st);
+            }
+            if (d.Cout >= 128) {
+                if (po3()) return V2CE_WS_RES(2, 3, 1, 2, 2, 3, 3, 0);
                 return V2CE_WS_RES(2, 3, 1, 2, 2, 4, 3, 0);
             }
             return V2CE_WS_RES(2, 3, 1, 1, 2, 4, 3, 0);
@@ -1919,11 +1867,9 @@ static int conv3d_dispatch(const v2ce_conv3d_desc *desc, const float *x0, const 
         // stride 2: the halo box is ~4x the output box, so 128-position boxes; one 32-channel fragment
         // row per wave measured best (Cout >= 128: 300-320; Cout = 64: 245)
         if (P.sc_w) {
-            static const bool na9 = [] { const char *e = getenv("V2CE_NA9"); return !(e && e[0] == '0'); }();
             // (128-channel tiles: both accumulator sets of four fragments and a nine-slot ring do not fit -- 173 spilled registers)
             if (d.Cout >= 128) return launch_f16x2_ws<3, 2, 4, 1, 4, 3, 2, 0>(P, d, st);
-            if (!small_co && na9) return launch_f16x2_ws<3, 2, 2, 1, 2, 9, 2, 0>(P, d, st);
-            if (!small_co) return launch_f16x2_ws<3, 2, 2, 1, 2, 3, 2, 0>(P, d, st);
+            if (!small_co) return launch_f16x2_ws<3, 2, 2, 1, 2, 9, 2, 0>(P, d, st);
             return launch_f16x2_ws<3, 2, 1, 1, 1, 3, 2, 0>(P, d, st);
         }
         if (d.Cout >= 128) return launch_f16x2_ws<3, 2, 4, 1, 4, 3>(P, d, st);
@@ -2070,21 +2016,6 @@ extern "C" int v2ce_conv3d_fwd_tail(const v2ce_conv3d_desc *desc, const float *x
                            tail_desc, tx0, tx1, thmap, twmap, tx0_absmax, tx1_absmax);
 }
 
-extern "C" int v2ce_conv3d_fwd_tail_pred(const v2ce_conv3d_desc *desc, const float *x0, const float *w_packed, const float *scale,
-                                         const float *shift, float *y, const float *x0_absmax, float *y_absmax, const void *pred_w,
-                                         const float *pred_b, int pred_cout, float *pred_y, const v2ce_conv3d_desc *tail_desc,
-                                         const float *tx0, const float *tx1, const int32_t *thmap, const int32_t *twmap,
-                                         const void *tail_w, const float *tx0_absmax, const float *tx1_absmax, const float *residual,
-                                         int res_h, int res_w_pitch, v2ce_stream_t stream) {
-    g_name_out = nullptr;
-    clear_error();
-    V2CE_REQUIRE(pred_w && tail_desc && tail_w, V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_tail_pred: null head weights / tail description / tail weights");
-    V2CE_REQUIRE(!residual || res_h > 0, V2CE_ERR_UNSUPPORTED, "v2ce_conv3d_fwd_tail_pred: the residual is the low-resolution one (res_h > 0)");
-    return conv3d_dispatch(desc, x0, nullptr, nullptr, nullptr, w_packed, scale, shift, residual, y, x0_absmax, nullptr, y_absmax, stream,
-                           pred_w, pred_b, pred_cout, pred_y, tail_w, nullptr, nullptr, nullptr, tail_desc, tx0, tx1, thmap, twmap,
-                           tx0_absmax, tx1_absmax, res_h, res_w_pitch);
-}
-
 extern "C" size_t v2ce_pack_pred_weights_f16x2_bytes(void) { return 2048 * 2 + 16; }
 
 extern "C" int v2ce_pack_pred_weights_f16x2(const float *w, int cout, int cin, void *table, v2ce_stream_t stream) {
@@ -2098,8 +2029,7 @@ extern "C" int v2ce_pack_pred_weights_f16x2(const float *w, int cout, int cin, v
 }
 
 extern "C" int v2ce_conv3d_variant_fused(const v2ce_conv3d_desc *desc, int mapped, int fuse_in, char *name, size_t cap) {
-    const bool tail_pred = (fuse_in & 8) != 0;              // the tail behind the conv with the fused head (v2ce_conv3d_fwd_tail_pred)
-    const int fuse = tail_pred ? 3 : fuse_in & 3;
+    const int fuse = fuse_in & 3;
     const bool with_res = (fuse_in & 4) != 0;
     V2CE_REQUIRE(name && cap > 0, V2CE_ERR_BAD_ARG, "v2ce_conv3d_variant: no buffer");
     name[0] = '\0';
@@ -2116,12 +2046,11 @@ extern "C" int v2ce_conv3d_variant_fused(const v2ce_conv3d_desc *desc, int mappe
     }
     const int rc = conv3d_dispatch(desc, nullptr, nullptr, m, m, nullptr, nullptr, nullptr, with_res ? &dummy : nullptr,
                                    nullptr, nullptr, nullptr, nullptr, nullptr,
-                                   (fuse == 1 || tail_pred) ? &dummy : nullptr, (fuse == 1 || tail_pred) ? &dummy : nullptr,
-                                   (fuse == 1 || tail_pred) ? 1 : 0, (fuse == 1 || tail_pred) ? const_cast<float *>(&dummy) : nullptr,
+                                   fuse == 1 ? &dummy : nullptr, fuse == 1 ? &dummy : nullptr,
+                                   fuse == 1 ? 1 : 0, fuse == 1 ? const_cast<float *>(&dummy) : nullptr,
                                    fuse >= 2 ? &dummy : nullptr, fuse == 2 ? &dummy : nullptr,
                                    fuse == 2 ? &dummy : nullptr, fuse == 2 ? const_cast<float *>(&dummy) : nullptr,
-                                   fuse == 3 ? &td : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                   (tail_pred && with_res && desc) ? (desc->Hout + 1) / 2 : 0, (tail_pred && with_res && desc) ? (desc->Wout + 1) / 2 : 0);
+                                   fuse == 3 ? &td : nullptr);
     g_name_out = nullptr;
     return rc;
 }

@@ -1,5 +1,6 @@
 // conv3d_dev.h -- device-side pieces shared by the conv translation units (conv3d.hip: generic kernels;
 // conv3d_up.hip: the phase-folded decoder kernel): launch parameters, the fused epilogues, range tracking.
+// (host-side pieces: conv3d_host.h)
 #pragma once
 #include "common.h"
 
@@ -153,6 +154,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams &P, f32x16 (&acc)
     // rpoff (C16, a residual): the residual is a 2x nearest-upsampled LOW-resolution tensor [B][T][Cout/16][rH][rWp][16]
     // (ConvParams::res_up): (*rpoff)[f] = byte offset of the position's group at (h >> 1, w >> 1) inside channel group 0 of its time
     // step there, or < 0
+    // DEAD CODE, kept on purpose: no caller in any translation unit passes rpoff since the last decoder block's split shortcut was
+    // removed (conv3d_wt.hip reads ConvParams::res_up in an epilogue of its own), so rup is false everywhere.  The
+    // parameter and its branch stay only because deleting them makes the compiler schedule 13 of the surviving
+    // conv3d_f16x2_ws_kernel instances differently (profiles/r08_retired_switches_static_parent_vs_branch.txt).
     typedef float f32x4q __attribute__((ext_vector_type(4)));
     typedef unsigned u32x4q __attribute__((ext_vector_type(4)));
     const float *__restrict__ scale = P.scale;

@@ -30,6 +30,7 @@
 //   * the skip channels' halo is staged with its columns DE-INTERLEAVED (even columns, then odd ones), so the
 //     stride-2 positions of a phase read consecutive 16-byte pieces.
 #include "conv3d_dev.h"
+#include "conv3d_host.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -73,14 +74,15 @@ struct UpParams {
     int zero0;                    // first piece of the zeroed region of an upsampled chunk's planes (edge tiles; >= plane0)
     int chs;                      // pieces per plane of the LDS buffers (>= the skip halo, >= zero0 + plane0)
     int stage_off;                // bytes from the start of LDS to the consumers' epilogue staging (4 x 4 KB)
-    int dbg;                      // timing experiments (V2CE_UP_DBG; WRONG results): 1 = stores dropped by the range check, 2 = no epilogue
+    int fold_plane;               // bytes between the hi and lo planes of the folded region (fold_off).  Not next to fold_off on purpose:
+                                  // it fills the slot a removed field had, so every other field keeps its kernarg offset; moved down, the
+                                  // kernels come out longer and spill more (profiles/r08_retired_switches_static_parent_vs_branch.txt)
     int HWh;                      // HWd / 2: first odd column of the de-interleaved skip halo
     int CG0;                      // C0 / 16
     int part;                     // 1: only the upsampled channels' chunks run (v2ce_conv3d_fwd_up2_part): the skip channels' share of the
                                   // convolution comes from another launch that adds this one's output as its residual
     int odd_h, odd_w;
     int fold_off;                 // bytes from wq to the folded region's hi plane
-    int fold_plane;               // bytes between its hi and lo planes
 };
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -707,27 +709,11 @@ __global__ __launch_bounds__(512, 1) void conv3d_up_kernel(UpParams U) {
         }
         [[maybe_unused]] const unsigned long long te = TICK();
         float *stage = reinterpret_cast<float *>(conv_smem + U.stage_off) + wave * 1024;       // this wave's 4 KB
-        if (U.dbg == 1) {
-#pragma unroll
-            for (int f = 0; f < PO_FR; ++f) poff[f] = -1;
-        }
-        if (U.dbg != 2) {
         up_epilogue<CO_FR, PO_FR>(P, acc, poff, co0, lane, T.b, inv_scale, stage, P.y, P.scale, P.shift, P.act, P.y_absmax);
         if constexpr (SC) {                                     // shortcut: bn_d(conv_d x), no activation, no range slot
             const float wd_scale = reinterpret_cast<const float *>(P.sc_w + 2 * wplane_d)[1];
             up_epilogue<CO_FR, PO_FR>(P, accd, poff, co0, lane, T.b, 1.0f / (x_scale * wd_scale), stage, P.sc_y, P.sc_scale, P.sc_shift,
                                       V2CE_ACT_NONE, nullptr);
-        }
-        } else {
-            float sink = 0.0f;
-#pragma unroll
-            for (int q = 0; q < CO_FR; ++q)
-#pragma unroll
-                for (int f = 0; f < PO_FR; ++f) {
-                    sink += acc[q][f][0];
-                    if constexpr (SC) sink += accd[q][f][0];
-                }
-            if (sink == 12345.678f) P.y[0] = sink;
         }
         ACC_T(t_epi, te);
         vb += (int)gridDim.x;
@@ -981,24 +967,15 @@ bool choose_up_cfg(UpCfg &out, int B, int T, int Ho, int Wo, int n_sub_max, int 
     return have;
 }
 
-thread_local char *g_up_name_out = nullptr;
-thread_local size_t g_up_name_cap = 0;
-
 template <int WCO, int CO_FR, int PO_FR, int FUSE>
 int launch_up(UpParams U, const v2ce_conv3d_desc &d, hipStream_t stream) {
     ConvParams &P = U.C;
     constexpr int CO_TILE = WCO * CO_FR * 32, NFG = PO_FR / WCO;
-    if (g_up_name_out) {
-        snprintf(g_up_name_out, g_up_name_cap, "conv3d_up_kernel<%d,%d,%d,%d>", WCO, CO_FR, PO_FR, FUSE);
+    if (g_name_out) {
+        snprintf(g_name_out, g_name_cap, "conv3d_up_kernel<%d,%d,%d,%d>", WCO, CO_FR, PO_FR, FUSE);
         return V2CE_OK;
     }
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            n = 256;
-        return n < 8 ? 8 : (n / 8) * 8;
-    }();
+    const int n_cu = persistent_cu_count();
     P.n_co_tiles = (d.Cout + CO_TILE - 1) / CO_TILE;
     // box, pitches and lane order: searched once per launch geometry
     UpCfg cfg{};
@@ -1058,7 +1035,7 @@ int launch_up(UpParams U, const v2ce_conv3d_desc &d, hipStream_t stream) {
     auto kern = conv3d_up_kernel<WCO, CO_FR, PO_FR, FUSE>;
     V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     P.total_blocks = (int)blocks;
-    const unsigned grid = (unsigned)(blocks > n_cu ? n_cu : blocks);
+    const unsigned grid = persistent_grid(blocks);
 #ifdef V2CE_STAMP
     V2CE_HIP_CHECK(hipMalloc(&P.stamps, (size_t)grid * 16 * sizeof(unsigned long long)));
     V2CE_HIP_CHECK(hipMemset(P.stamps, 0, (size_t)grid * 16 * sizeof(unsigned long long)));
@@ -1155,7 +1132,7 @@ static int up_dispatch(const v2ce_conv3d_desc *desc, const float *x0, const floa
                        const float *x1_absmax, float *y_absmax, const void *sc_w, const float *sc_scale,
                        const float *sc_shift, float *sc_y, v2ce_stream_t stream, bool part = false) {
     clear_error();
-    V2CE_REQUIRE(desc && (g_up_name_out || (x0 && (x1 || part) && w_up && scale && shift && y)), V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_up2: null pointer");
+    V2CE_REQUIRE(desc && (g_name_out || (x0 && (x1 || part) && w_up && scale && shift && y)), V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_up2: null pointer");
     V2CE_REQUIRE(!part || !sc_w, V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_up2_part: no fused shortcut on a partial launch");
     const v2ce_conv3d_desc &d = *desc;
     V2CE_REQUIRE(d.B > 0 && d.T > 0 && d.C0 > 0 && d.C1 > 0 && d.Hin > 0 && d.Win > 0 && d.Cout > 0, V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_up2: bad shape");
@@ -1175,7 +1152,7 @@ static int up_dispatch(const v2ce_conv3d_desc *desc, const float *x0, const floa
                  "v2ce_conv3d_fwd_up2: a single sequence exceeds the 2 GiB buffer-descriptor range");
     V2CE_REQUIRE(x0_absmax || !x1_absmax, V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_up2: x1_absmax without x0_absmax");
     V2CE_REQUIRE(!x0_absmax || x1_absmax, V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_up2: x0_absmax without x1_absmax");
-    V2CE_REQUIRE(!sc_w || (d.Cout <= 32 && sc_scale && sc_shift && (sc_y || g_up_name_out)), V2CE_ERR_UNSUPPORTED,
+    V2CE_REQUIRE(!sc_w || (d.Cout <= 32 && sc_scale && sc_shift && (sc_y || g_name_out)), V2CE_ERR_UNSUPPORTED,
                  "v2ce_conv3d_fwd_up2: the fused shortcut needs <= 32 output channels and its scale / shift / output");
     const size_t total = v2ce_pack_weights_f16x2_up_bytes(d.Cout, d.C0, d.C1);
     V2CE_REQUIRE(total < (1ull << 31), V2CE_ERR_UNSUPPORTED, "v2ce_conv3d_fwd_up2: the weight buffer exceeds the 2 GiB buffer-descriptor range");
@@ -1199,20 +1176,14 @@ static int up_dispatch(const v2ce_conv3d_desc *desc, const float *x0, const floa
     U.odd_h = d.Hout & 1; U.odd_w = d.Wout & 1;
     U.fold_off = (int)up_fold_off(d.Cout, P.Cin);
     U.fold_plane = (int)((size_t)kUpSlots * d.C0 * d.Cout * 2);
-    { const char *e = getenv("V2CE_UP_DBG"); U.dbg = e ? atoi(e) : 0; }
     hipStream_t st = as_stream(stream);
     if (sc_w) return launch_up<1, 1, 4, 2>(U, d, st);
     if (d.Cout <= 32) return launch_up<1, 1, 4, 0>(U, d, st);
     // >= 64 output channels: 128 channels x 256 positions (two phases per wave), 64 x 512 (one phase per wave) or 64 x 256 (the same at
     // half the positions) -- whichever walks the CUs in the fewest tile-equivalents (whole rounds of the persistent grid x tile size).
     // dec0 (33 x 44 planes, 256 channels): 800 tiles of 128 x 256 are FOUR rounds on 256 CUs where 3.1 would do; 1 600 half tiles
-    // are seven half rounds.  V2CE_UP_TILE = 0 (choose) | 1 | 2 | 3 forces one of the three.
-    static const int force = [] { const char *e = getenv("V2CE_UP_TILE"); return e ? atoi(e) : 0; }();
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-        return n < 8 ? 8 : (n / 8) * 8;
-    }();
+    // are seven half rounds.
+    const int n_cu = persistent_cu_count();
     auto cost = [&](int co_tile, int n_sub_max, int nfg, double size) -> double {      // rounds x tile size, for the best box of that shape
         UpCfg c{};
         const int n_co = (d.Cout + co_tile - 1) / co_tile;
@@ -1222,27 +1193,25 @@ static int up_dispatch(const v2ce_conv3d_desc *desc, const float *x0, const floa
         const long long blocks = 8 * ((nsp + 7) / 8) * n_co;
         return (double)((blocks + n_cu - 1) / n_cu) * size;
     };
-    int pick = force;
-    if (!pick) {
-        {
-            static std::mutex mu;
-            static std::map<std::tuple<int, int, int, int, int, int, int>, int> cache;
-            std::lock_guard<std::mutex> g(mu);
-            const auto key = std::make_tuple(d.B, d.T, d.Hout, d.Wout, d.C0, d.C1, d.Cout);
-            auto it = cache.find(key);
-            if (it == cache.end()) {
-                const double c1 = d.Cout >= 128 ? cost(128, 64, 2, 1.0) : 1e30, c2 = cost(64, 128, 4, 1.0), c3 = cost(64, 64, 2, 0.5);
-                // (the half tile pays twice the weight stream per MFMA: it must save at least 8 % to be taken)
-                int p = d.Cout >= 128 ? 1 : 2;
-                double best = p == 1 ? c1 : c2;
-                if (c2 < best - 1e-9) { p = 2; best = c2; }
-                if (c3 < 0.92 * best) p = 3;
-                it = cache.emplace(key, p).first;
-            }
-            pick = it->second;
+    int pick;
+    {
+        static std::mutex mu;
+        static std::map<std::tuple<int, int, int, int, int, int, int>, int> cache;
+        std::lock_guard<std::mutex> g(mu);
+        const auto key = std::make_tuple(d.B, d.T, d.Hout, d.Wout, d.C0, d.C1, d.Cout);
+        auto it = cache.find(key);
+        if (it == cache.end()) {
+            const double c1 = d.Cout >= 128 ? cost(128, 64, 2, 1.0) : 1e30, c2 = cost(64, 128, 4, 1.0), c3 = cost(64, 64, 2, 0.5);
+            // (the half tile pays twice the weight stream per MFMA: it must save at least 8 % to be taken)
+            int p = d.Cout >= 128 ? 1 : 2;
+            double best = p == 1 ? c1 : c2;
+            if (c2 < best - 1e-9) { p = 2; best = c2; }
+            if (c3 < 0.92 * best) p = 3;
+            it = cache.emplace(key, p).first;
         }
+        pick = it->second;
     }
-    if (pick == 1 && d.Cout >= 128) return launch_up<2, 2, 4, 0>(U, d, st);
+    if (pick == 1) return launch_up<2, 2, 4, 0>(U, d, st);
     if (pick == 3) return launch_up<1, 2, 2, 0>(U, d, st);
     return launch_up<1, 2, 4, 0>(U, d, st);
 }
@@ -1251,25 +1220,25 @@ extern "C" int v2ce_conv3d_fwd_up2(const v2ce_conv3d_desc *desc, const float *x0
                                    const float *scale, const float *shift, float *y, const float *x0_absmax,
                                    const float *x1_absmax, float *y_absmax, const void *sc_w, const float *sc_scale,
                                    const float *sc_shift, float *sc_y, v2ce_stream_t stream) {
-    g_up_name_out = nullptr;
+    g_name_out = nullptr;
     return up_dispatch(desc, x0, x1, w_up, scale, shift, y, x0_absmax, x1_absmax, y_absmax, sc_w, sc_scale, sc_shift, sc_y, stream);
 }
 
 extern "C" int v2ce_conv3d_fwd_up2_part(const v2ce_conv3d_desc *desc, const float *x0, const void *w_up, const float *scale, const float *shift,
                                         float *y, const float *x0_absmax, const float *x1_absmax, float *y_absmax, v2ce_stream_t stream) {
-    g_up_name_out = nullptr;
+    g_name_out = nullptr;
     return up_dispatch(desc, x0, nullptr, w_up, scale, shift, y, x0_absmax, x1_absmax, y_absmax, nullptr, nullptr, nullptr, nullptr, stream, true);
 }
 
 extern "C" int v2ce_conv3d_up2_variant(const v2ce_conv3d_desc *desc, int with_shortcut, char *name, size_t cap) {
     V2CE_REQUIRE(name && cap > 0, V2CE_ERR_BAD_ARG, "v2ce_conv3d_up2_variant: no buffer");
     name[0] = '\0';
-    g_up_name_out = name;
-    g_up_name_cap = cap;
+    g_name_out = name;
+    g_name_cap = cap;
     static const float dummy = 0.0f;
     const int rc = up_dispatch(desc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                with_shortcut ? &dummy : nullptr, with_shortcut ? &dummy : nullptr, with_shortcut ? &dummy : nullptr,
                                nullptr, nullptr);
-    g_up_name_out = nullptr;
+    g_name_out = nullptr;
     return rc;
 }

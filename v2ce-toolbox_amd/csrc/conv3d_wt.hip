@@ -23,6 +23,7 @@
 //     residual, activation, range tracking -- the same code as the direct kernel).  The producers take part in the 2 * CO_FR extra
 //     barriers before they refill that buffer.
 #include "conv3d_dev.h"
+#include "conv3d_host.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -972,9 +973,6 @@ int wt_pack_launch(const WtBatch &B, int pass, hipStream_t st) {
     return V2CE_OK;
 }
 
-thread_local char *g_wt_name_out = nullptr;
-thread_local size_t g_wt_name_cap = 0;
-
 struct WtBox { int pp, th, tw, flat; };     // flat > 0: ranges of `flat` positions of the plane instead of th x tw rectangles
 
 // The box (pairs x rows x columns) of a tile: at most PO_FR * 32 pair-positions, at most 256 halo elements (one per producer
@@ -995,9 +993,8 @@ WtBox choose_wt_box(int B, int T, int H, int W, int n_co, int n_cu, int pos_tile
     const int pairs = (T + 1) / 2;
     WtBox best{0, 0, 0, 0};
     double best_cost = 1e30;
-    static const int flat_mode = [] { const char *e = getenv("V2CE_WT_FLAT"); return e ? atoi(e) : 1; }();
     // ranges of the row-major plane (narrow planes): n positions span at most (W - 1 + n - 1) / W + 1 rows of W + 2 halo columns
-    for (int pp = 1; flat_mode && pp <= pairs && pp <= 16; ++pp) {
+    for (int pp = 1; pp <= pairs && pp <= 16; ++pp) {
         const int n_max = pos_tile / pp;
         if (n_max < 1) break;
         const int nR = (H * W + n_max - 1) / n_max, n = (H * W + nR - 1) / nR;
@@ -1029,18 +1026,13 @@ WtBox choose_wt_box(int B, int T, int H, int W, int n_co, int n_cu, int pos_tile
 template <int CO_FR, int PO_FR, int RES, bool TAIL = false>
 int launch_wt(ConvParams P, const v2ce_conv3d_desc &d, hipStream_t stream) {
     constexpr int CO_TILE = CO_FR * 32, POS_TILE = PO_FR * 32;
-    if (g_wt_name_out) {
-        snprintf(g_wt_name_out, g_wt_name_cap, "conv3d_wt_kernel<%d,%d,%d,%d>", CO_FR, PO_FR, RES, (int)TAIL);
+    if (g_name_out) {
+        snprintf(g_name_out, g_name_cap, "conv3d_wt_kernel<%d,%d,%d,%d>", CO_FR, PO_FR, RES, (int)TAIL);
         return V2CE_OK;
     }
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-        return n < 8 ? 8 : (n / 8) * 8;
-    }();
     P.n_co_tiles = (d.Cout + CO_TILE - 1) / CO_TILE;
     WtBox bx{d.tile_t / 2, d.tile_h, d.tile_w, 0};
-    if (bx.pp <= 0 || bx.th <= 0 || bx.tw <= 0) bx = choose_wt_box(d.B, d.T, d.Hout, d.Wout, P.n_co_tiles, n_cu, POS_TILE);
+    if (bx.pp <= 0 || bx.th <= 0 || bx.tw <= 0) bx = choose_wt_box(d.B, d.T, d.Hout, d.Wout, P.n_co_tiles, persistent_cu_count(), POS_TILE);
     V2CE_REQUIRE(bx.pp > 0 && bx.th > 0 && bx.tw > 0, V2CE_ERR_UNSUPPORTED, "v2ce_conv3d_fwd_wt: no box fits");
     P.TT = 2 * bx.pp; P.TH = bx.th; P.TW = bx.tw;
     P.flat = bx.flat;
@@ -1052,12 +1044,9 @@ int launch_wt(ConvParams P, const v2ce_conv3d_desc &d, hipStream_t stream) {
     V2CE_REQUIRE(P.n_pos <= POS_TILE && P.plane <= kWtSlot, V2CE_ERR_UNSUPPORTED, "v2ce_conv3d_fwd_wt: tile does not fit");
     P.n_spatial = d.B * P.nT * P.nH * P.nW;
     P.per_xcd = (P.n_spatial + 7) / 8;
-    {
-        // weights of a channel tile vs the input of the XCD's boxes: walk the larger one once
-        static const int force = [] { const char *e = getenv("V2CE_WT_ORDER"); return e ? atoi(e) : 0; }();
-        const double w_bytes = (double)CO_TILE * P.Cin * kWtTaps * 4, x_bytes = (double)P.per_xcd * P.n_pos * 2 * P.Cin * 4;
-        P.xcd_remap = force ? force : (P.n_co_tiles > 1 && w_bytes * P.n_co_tiles > x_bytes ? 2 : 1);
-    }
+    // weights of a channel tile vs the input of the XCD's boxes: walk the larger one once
+    const double w_bytes = (double)CO_TILE * P.Cin * kWtTaps * 4, x_bytes = (double)P.per_xcd * P.n_pos * 2 * P.Cin * 4;
+    P.xcd_remap = P.n_co_tiles > 1 && w_bytes * P.n_co_tiles > x_bytes ? 2 : 1;
     const long long blocks = (long long)8 * P.per_xcd * P.n_co_tiles;
     P.total_blocks = (int)blocks;
     const size_t lds = (size_t)kWtChs * (2 * 4 * 16) + 2 * 2 * CO_TILE * sizeof(float);  // 128 KB of pieces + two scale | shift tables
@@ -1070,7 +1059,7 @@ int launch_wt(ConvParams P, const v2ce_conv3d_desc &d, hipStream_t stream) {
     if (getenv("V2CE_WT_VERBOSE"))
         fprintf(stderr, "[wt<%d,%d,%d%s> %dx%dx%dx%d C %d -> %d] box %d pairs x %d x %d%s (%d of %d positions, %d halo elements), %lld tiles\n", CO_FR, PO_FR, RES, TAIL ? ",tail" : "", d.B, d.T,
                 d.Hout, d.Wout, P.Cin, P.Cout, bx.pp, bx.th, bx.tw, bx.flat ? " rows: flat ranges" : "", P.n_pos, POS_TILE, P.plane, blocks);
-    const unsigned grid = (unsigned)(blocks > n_cu ? n_cu : blocks);
+    const unsigned grid = persistent_grid(blocks);
 #ifdef V2CE_STAMP
     V2CE_HIP_CHECK(hipMalloc(&P.stamps, (size_t)grid * 16 * sizeof(unsigned long long)));
     V2CE_HIP_CHECK(hipMemset(P.stamps, 0, (size_t)grid * 16 * sizeof(unsigned long long)));
@@ -1113,7 +1102,7 @@ struct WtTail {
 int wt_dispatch(const v2ce_conv3d_desc *desc, const float *x, const void *w_wt, const float *scale, const float *shift,
                 const float *residual, float *y, const float *x_absmax, float *y_absmax, v2ce_stream_t stream, const WtTail *tl = nullptr) {
     clear_error();
-    V2CE_REQUIRE(desc && (g_wt_name_out || (x && w_wt && scale && shift && y)), V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_wt: null pointer");
+    V2CE_REQUIRE(desc && (g_name_out || (x && w_wt && scale && shift && y)), V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_wt: null pointer");
     const v2ce_conv3d_desc &d = *desc;
     V2CE_REQUIRE(d.B > 0 && d.T > 0 && d.C0 > 0 && d.C1 == 0 && d.Hin > 0 && d.Win > 0 && d.Cout > 0, V2CE_ERR_BAD_ARG,
                  "v2ce_conv3d_fwd_wt: bad shape (one source: C1 must be 0)");
@@ -1157,7 +1146,7 @@ int wt_dispatch(const v2ce_conv3d_desc *desc, const float *x, const void *w_wt, 
                      V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_wt_tail: the tail must be a 1x1x1 conv (channels-last-16, channel counts multiples "
                      "of 16) producing exactly the main conv's output shape");
         V2CE_REQUIRE(((t.C0 + t.C1) / 16) % 4 == 0, V2CE_ERR_UNSUPPORTED, "v2ce_conv3d_fwd_wt_tail: the tail's channel count must be a multiple of 64");
-        V2CE_REQUIRE((g_wt_name_out || tl->tx0) && (t.C1 == 0 || tl->tx1 || g_wt_name_out) && (tl->thmap == nullptr) == (tl->twmap == nullptr) &&
+        V2CE_REQUIRE((g_name_out || tl->tx0) && (t.C1 == 0 || tl->tx1 || g_name_out) && (tl->thmap == nullptr) == (tl->twmap == nullptr) &&
                      (tl->thmap || (t.H0 == t.Hin && t.W0 == t.Win)), V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_wt_tail: tail inputs / index maps");
         V2CE_REQUIRE((tl->tx0_absmax != nullptr) == (x_absmax != nullptr) && (t.C1 == 0 || !tl->tx0_absmax || tl->tx1_absmax), V2CE_ERR_BAD_ARG,
                      "v2ce_conv3d_fwd_wt_tail: range slots of the tail inputs");
@@ -1171,7 +1160,7 @@ int wt_dispatch(const v2ce_conv3d_desc *desc, const float *x, const void *w_wt, 
         if (residual) return launch_wt<2, 4, 1, true>(P, d, st);
         return launch_wt<2, 4, 0, true>(P, d, st);
     }
-    if (residual || (g_wt_name_out && scale)) return launch_wt<2, 4, 1>(P, d, st);
+    if (residual || (g_name_out && scale)) return launch_wt<2, 4, 1>(P, d, st);
     return launch_wt<2, 4, 0>(P, d, st);
 }
 
@@ -1228,7 +1217,7 @@ extern "C" int v2ce_pack_weights_f16x2_wt(const float *w, int Cout, int Cin, con
 
 extern "C" int v2ce_conv3d_fwd_wt(const v2ce_conv3d_desc *desc, const float *x, const void *w_wt, const float *scale, const float *shift,
                                   const float *residual, float *y, const float *x_absmax, float *y_absmax, v2ce_stream_t stream) {
-    g_wt_name_out = nullptr;
+    g_name_out = nullptr;
     return wt_dispatch(desc, x, w_wt, scale, shift, residual, y, x_absmax, y_absmax, stream);
 }
 
@@ -1237,7 +1226,7 @@ extern "C" int v2ce_conv3d_fwd_wt_tail(const v2ce_conv3d_desc *desc, const float
                                        const float *tx1, const int32_t *thmap, const int32_t *twmap, const void *tail_w,
                                        const float *tx0_absmax, const float *tx1_absmax, const float *residual, int res_h, int res_w_pitch,
                                        v2ce_stream_t stream) {
-    g_wt_name_out = nullptr;
+    g_name_out = nullptr;
     const WtTail tl{tail_desc, tx0, tx1, thmap, twmap, tail_w, tx0_absmax, tx1_absmax, res_h, res_w_pitch};
     return wt_dispatch(desc, x, w_wt, scale, shift, residual, y, x_absmax, y_absmax, stream, &tl);
 }
@@ -1245,8 +1234,8 @@ extern "C" int v2ce_conv3d_fwd_wt_tail(const v2ce_conv3d_desc *desc, const float
 extern "C" int v2ce_conv3d_wt_variant(const v2ce_conv3d_desc *desc, int with_residual, char *name, size_t cap) {
     V2CE_REQUIRE(name && cap > 0, V2CE_ERR_BAD_ARG, "v2ce_conv3d_wt_variant: no buffer");
     name[0] = '\0';
-    g_wt_name_out = name;
-    g_wt_name_cap = cap;
+    g_name_out = name;
+    g_name_cap = cap;
     static const float dummy = 0.0f;
     int rc;
     if (with_residual == 2) {                              // the tail variant (any valid tail description names the same kernel)
@@ -1262,6 +1251,6 @@ extern "C" int v2ce_conv3d_wt_variant(const v2ce_conv3d_desc *desc, int with_res
     } else {
         rc = wt_dispatch(desc, nullptr, nullptr, with_residual ? &dummy : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     }
-    g_wt_name_out = nullptr;
+    g_name_out = nullptr;
     return rc;
 }
