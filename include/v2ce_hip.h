@@ -132,9 +132,7 @@ int v2ce_ldati_status(const void *workspace, int B, int H, int W, double fps, do
 /* The two-level plan v2ce_ldati_emit would use (introspection for tools/tests): info [10] = {ok, fine-key
  * bits (shift), coarse buckets per segment, tiles per frame, tile-pass capacity, sort capacity, entries
  * of the per-tile tables, entries of the per-bucket tables, LDS bytes of the tile pass, of the sort}.
- * Workspace layout (u32 units): bofs [n_bkt = B*9*(NB+1)] | groups [B*9*NB] | big_list [B*9*NB] | ngroups [B*9] |
- * seg_flag [B*9] | status [4] = {status, number of big buckets, -, -} | records [total] |
- * roff [n_tab = B*9*T*(NB+1)] as u16. */
+ * Workspace layout: struct TwoLevelWs in v2ce-toolbox_amd/csrc/ldati_plan.h (the one definition: sizes, offsets, the status word). */
 /* Fused count + sparse tile pass (round 4).  v2ce_ldati_count reads the voxel grid once to
  * count and v2ce_ldati_emit reads it again to compute the timestamps.  On real UNet output every 2048-pixel tile is sparse
  * (<= 8192 events over the nine bins): v2ce_ldati_count_fused does both in ONE pass -- it returns exactly what

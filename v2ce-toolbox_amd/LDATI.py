@@ -145,7 +145,7 @@ _PINNED = _PinnedPool()
 # densest-segment event count of the previous call with the same shape and options: the fused count pass assumes the
 # bucket geometry that follows from it (consecutive batches of a clip agree; a miss costs one two-pass call)
 _SEG_HINT = {}
-_SPARSE_TILE_CAP = 8192                  # kSparseCap of csrc/ldati.hip: events of one tile (all nine bins) the fused pass holds
+_SPARSE_TILE_CAP = 8192                  # kSparseCap of csrc/ldati_const.h: events of one tile (all nine bins) the fused pass holds
 
 
 class PendingLdati:

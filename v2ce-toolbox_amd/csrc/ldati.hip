@@ -24,13 +24,20 @@
 //   bucket sort: workgroup per (segment, bucket): gathers the tiles' runs in tile order (= pixel
 //                order), one stable counting sort on (fine key, category) in LDS, and writes the
 //                final 13-byte packed records (or SoA) as full coalesced lines.
-//   sweep      : the v1 kernel (one workgroup per segment, whole key histogram in LDS) remains the
-//                fallback for segments with a bucket beyond the LDS capacity (degenerate ties) and
-//                for workspace == NULL; both paths are bit-identical.
+//   big buckets: coarse buckets beyond the LDS capacity of a sort workgroup (degenerate ties) are ordered
+//                by ldati_big_bucket_kernel inside the same call.
+//   sweep      : the v1 kernel (one workgroup per segment, whole key histogram in LDS) serves
+//                workspace == NULL only; both paths are bit-identical.
+//
+// ldati_dev.h holds LdatiParams, the device helpers and the __device__ globals; ldati_plan.h the host-side
+// planning (sizes, workspace layouts, path choice); ldati_const.h the constants both read; this file the
+// kernels and the entry points.  One translation unit: the globals must exist once.
 //
 // Arithmetic is bit-exact w.r.t. the CPU reference: every f32/f64 operation is a separate IEEE
 // operation (-ffp-contract=off, correctly rounded '/' and sqrt), in the reference's order.
 #include "common.h"
+#include "ldati_dev.h"
+#include "ldati_plan.h"
 
 #include <atomic>
 #include <mutex>
@@ -43,578 +50,6 @@
 
 namespace v2ce {
 namespace {
-
-constexpr int kTilePix = 2048;        // pixels of one polarity plane per tile
-constexpr int kLocalBits = 11;        // log2(kTilePix)
-constexpr int kCountThreads = 512;
-constexpr int kMaxTiles = 512;        // tiles per frame (both polarities) the bucket sort indexes
-constexpr int kMaxNB = 512;           // coarse buckets per segment
-constexpr int kMaxShift = 8;          // log2 of the widest coarse bucket
-constexpr int kMaxSpanKeys = 128;     // timestamps a sort group spans at most (its histogram has 4x as many bins)
-constexpr int kSmallGroupSpanKeys = 256;   // ... in the small-group regime (make_plan; measured 128 / 256 / 512: e2e sort 94 / 89 / 116 us)
-constexpr int kCapTile = 15360;       // events of one (tile, bin) the tile pass can hold in LDS
-#ifndef V2CE_SPARSE_CAP               // (diagnostic builds: tools/sparse_cap_ab.sh)
-#define V2CE_SPARSE_CAP 8192
-#endif
-#ifndef V2CE_SPARSE_WAVES
-#define V2CE_SPARSE_WAVES 1
-#endif
-constexpr int kSparseCap = V2CE_SPARSE_CAP;      // events of one tile over all nine bins the sparse tile kernel holds
-constexpr int kSparseThreads = 512;
-constexpr size_t kSparseLds = (size_t)(2 * kSparseCap + kSparseThreads * 5 + 34) * 4 + 9 * 8 + (kSparseThreads / 64) * 10 * 4;
-constexpr int kSlopeM = 31;            // slope table (g_slope_tab): |count difference| <= kSlopeM, count <= kSlopeM; else computed
-constexpr int kSlopeTab = (2 * kSlopeM + 1) * (kSlopeM + 1);
-// sort workgroups: 256 threads (dense segments) or 128 (make_plan)
-
-struct LdatiParams {
-    const float *vox;
-    int B, H, W, HW;
-    // scalars of LDATI.py:145-146 cast the way CPU torch casts python scalars
-    double fps;        // python number used in the f64 single-event path
-    float VS, VS2, INV, FPS;
-    float RFPS, R9;    // f32(1 / FPS), f32(1 / 9): reciprocals of the two constant divisors of the k == 0 time (k0_time)
-    double RFPS64, R9_64;   // RN(1 / fps), RN(1 / 9) in f64: the single-event time's two constant divisors (single_key_fast)
-    int fast_slot;     // slot of g_fastdiv that holds the exhaustive check of k0_time's fast form for this FPS, or -1
-    float offt[9];     // f32(arange(0,1/fps,1/fps/9)[c]) + f32(t0)
-    long long kbase[9];  // key = timestamp - kbase[c], clamped to [0, NK)
-    int NK, nbits;
-    int ts32;          // every timestamp and key base fits int32: the f32 -> int conversions use 32 bits
-    int strategy;      // V2CE_STRATEGY_*: NONE drops every multi-event voxel (LDATI.py:206-207,241)
-    int bidir;         // bidirectional relocation (LDATI.py:107-122)
-    const float2 *kbb; // pooled slope parameters {k, b} [B][2][9][HW] (LDATI.py:177-190), or null
-    unsigned long long *keys;     // generic path ('random'): one 64-bit sort key per event, or null
-    int rng_mode;
-    const float *uniforms;
-    int replay_max_n;
-    unsigned long long seed;
-    long long frame_base;
-    const long long *seg_offsets;
-    const long long *frame_ts_add;
-    long long *ts;                // SoA outputs (all four or none)
-    short *x;
-    short *y;
-    signed char *p;
-    unsigned char *packed;        // or 13-byte packed records
-    // two-level path
-    int shift, NB, nb1;           // coarse bucket = key >> shift; nb1 = bits of a bucket index
-    int T, tpp;                   // tiles per frame (2*tpp), tiles per polarity plane
-    int PB;                       // bits of a pixel index
-    int capA, cap2;               // LDS capacities (records) of the tile pass / the bucket sort
-    int tbits;                    // binary-search steps over the tiles of a frame
-    const unsigned *tile_off;     // [B][T][9] exclusive prefix of the tile counts inside the segment
-    const unsigned *tc;           // [B][T][9] the tile counts themselves
-    int sparse_cap;               // tiles with at most this many events (all nine bins) go to the sparse tile kernel; 0 = none
-    unsigned short *roff;         // [B*9][T][NB+1] per tile: exclusive prefix of its bucket counts (last = tile total <= kCapTile)
-    unsigned *bofs;               // [B*9][NB+1] exclusive prefix of the bucket totals inside the segment
-    unsigned *groups;             // [B*9][NB] sort groups: first bucket | (end bucket << 16)
-    unsigned *ngroups;            // [B*9]
-    unsigned *big_list;           // [B*9*NB] coarse buckets beyond cap2: (segment << 16) | bucket
-    unsigned *nbig;               // [1] their number
-    int span;                     // most coarse buckets a sort group may cover (key span <= kMaxSpanKeys)
-    int hist_bins;                // bins reserved per wave in the sort's LDS histogram
-    unsigned *temp;               // [total events] 4-byte records (fine | multi | local pixel)
-    int *seg_flag;                // [B*9] 1 = a bucket exceeds cap2 -> segment goes to the sweep kernel
-    int *status;                  // [1] != 0: a flagged segment could not be swept (NK too large)
-    int sweep_ok;
-    int ballot_ranks;             // 1 = ignore g_lds_order_ok and rank with the ballot match-any (V2CE_LDATI_NO_ATOMIC_ORDER=1: the
-                                  // fallback a device that fails the probe would take, forced so that tests can run it)
-    // fused count + sparse tile pass (v2ce_ldati_count_fused): every tile owns a slot of kSparseCap records
-    unsigned *tc_w;               // [B][T][9] tile counts, written by the fused kernel
-    unsigned long long *stats_w;  // [5] max voxel count | - | - | - | largest tile total (all nine bins)
-    unsigned *tile_abs_w;         // [B*9][T] record index of the (tile, bin) run inside `temp`
-    const unsigned *tile_abs;     // the same, read by the bucket sort (null: runs at seg_offsets + tile_off)
-    const int *fused_status;      // status word of the fused kernel, folded into `status` by the bucket scan
-    int slot_cap;                 // > 0: ldati_tile_dense_kernel is ALSO the count pass (v2ce_ldati_count_fused in the dense regime): every
-                                  // (tile, bin) run goes to its own slot of slot_cap (= capA) records, counts to tc_w, maxima to stats_w
-    int Tp;                       // T rounded up to a multiple of 8
-    unsigned *gruns;              // [B*9][NB][Tp] per sort group and tile: run start inside the tile's (tile, bin) run | records << 16,
-                                  // written by the bucket scan (which has the run table in L2 anyway) so that a sort workgroup's
-                                  // setup is ONE contiguous row instead of two 938-byte-strided loads per tile
-    const unsigned *tile_src;     // [B*9][Tp] record index of the (tile, bin) run relative to the sort's base, one contiguous row per
-                                  // segment (two-pass: tile_off transposed by the tile scan; fused: the slot starts)
-};
-
-// ---- Philox4x32-10, counter (pixel, j>>2, p*9+c, frame), key = seed ---------------------------
-__device__ __forceinline__ void philox4(unsigned long long seed, unsigned pixel, unsigned jb,
-                                        unsigned pc, unsigned frame, unsigned (&out)[4]) {
-    unsigned c0 = pixel, c1 = jb, c2 = pc, c3 = frame;
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0; c1 = (unsigned)p1; c2 = n2; c3 = (unsigned)p0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-__device__ __forceinline__ float u24(unsigned w) { return (float)(w >> 8) * (1.0f / 16777216.0f); }
-
-__device__ __forceinline__ float philox_uniform(unsigned long long seed, unsigned pixel, unsigned j,
-                                                unsigned pc, unsigned frame) {
-    unsigned o[4];
-    philox4(seed, pixel, j >> 2, pc, frame, o);
-    const unsigned sel = j & 3u;
-    return u24(sel == 0 ? o[0] : sel == 1 ? o[1] : sel == 2 ? o[2] : o[3]);
-}
-
-// ---- relocation recurrence (LDATI.py:94-106) up to bin `last` ----------------------------------
-// yv[i] holds voxel bin i of this lane's pixel (i <= last, plus yv[9] when last == 8).
-// Returns the counts of bins c-1, c, c+1 and the debt of bin c.
-__device__ __forceinline__ void relocate_bins(const float (&yv)[10], int c, int last, int &n_l,
-                                              int &n_c, int &n_r, float &debt_c) {
-    const float eps = 1e-6f;
-    float d = 0.0f;
-    n_l = n_c = n_r = 0;
-    debt_c = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        if (i <= last) {
-            const float r = yv[i] - d;
-            const float cc = ceilf(r - eps);
-            d = cc - r;
-            int ni = (int)cc;
-            if (i == 8) ni += (int)(yv[9] - d);   // LDATI.py:106
-            if (i == c - 1) n_l = ni;
-            if (i == c) { n_c = ni; debt_c = d; }
-            if (i == c + 1) n_r = ni;
-        }
-    }
-}
-
-__device__ __forceinline__ void load_bins(const float *plane0, long long HW, int px, bool valid,
-                                          int last, float (&yv)[10]) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const bool need = (i <= last) || (i == 9 && last == 8);
-        yv[i] = (need && valid) ? plane0[(long long)i * HW + px] : 0.0f;
-    }
-}
-
-// all nine bins of one pixel at once: counts and tendencies (LDATI.py:94-106, or :107-122 when bidir)
-__device__ __forceinline__ void relocate_all(const float (&yv)[10], bool bidir, int (&n)[9], float (&tend)[9]) {
-    const float eps = 1e-6f;
-    float d = 0.0f;
-    if (!bidir) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            const float r = yv[i] - d;
-            const float cc = ceilf(r - eps);
-            d = cc - r;
-            n[i] = (int)cc;
-            tend[i] = d;
-        }
-        n[8] += (int)(yv[9] - d);
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float r = yv[i] - d;
-        const float cc = ceilf(r - eps);
-        d = cc - r;
-        n[i] = (int)cc;
-        tend[i] = d;
-    }
-    n[4] = 0;                                  // never written by the reference's bidirectional branch
-    tend[4] = 0.0f;
-    float bless = yv[9];
-#pragma unroll
-    for (int i = 8; i > 5; --i) {
-        tend[i] = bless;
-        float t = yv[i] + bless;
-        t = floorf(t + eps);
-        bless = (yv[i] - t) + bless;
-        bless = bless < 0.0f ? 0.0f : bless;
-        n[i] = (int)t;
-    }
-    tend[5] = bless - d;
-    n[5] = (int)ceilf((yv[5] + bless) - d);
-}
-
-// a[c] for a wave-uniform c without dynamic register indexing
-template <typename T>
-__device__ __forceinline__ T pick9(const T (&a)[9], int c) {
-    T v = a[0];
-#pragma unroll
-    for (int i = 1; i < 9; ++i) v = c == i ? a[i] : v;
-    return v;
-}
-
-// single-event timestamp, all f64 (LDATI.py:156-165)
-__device__ __forceinline__ long long single_ts(float debt, double fps, float offt) {
-    double t = (double)debt / fps / 9.0;
-    t += (double)offt;
-    t *= 1e6;
-    return (long long)t;
-}
-
-// slope parameters of one multi-event voxel, f32 (LDATI.py:188-190 with :25-45 folded in)
-__device__ __forceinline__ void slope_params(int n_l, int n_c, int n_r, int c, const LdatiParams &P,
-                                             float &k, float &bb, const float2 *tab = nullptr) {
-    if (tab) {                                                 // the tabulated results of the expressions below
-        const int d = (c == 0 || c == 8) ? 0 : n_r - n_l;
-        if (d >= -kSlopeM && d <= kSlopeM && n_c >= 0 && n_c <= kSlopeM && n_l >= 0 && n_r >= 0 && n_l < (1 << 23) && n_r < (1 << 23)) {
-            const float2 kb = tab[(d + kSlopeM) * (kSlopeM + 1) + n_c];
-            k = kb.x; bb = kb.y;
-            return;
-        }
-    }
-    // reflect padding makes the central difference vanish at the first and last bin
-    const float sxy = (c == 0 || c == 8) ? 0.0f : ((float)n_r - (float)n_l);
-    const float k0 = (3.0f * sxy) / 6.0f;
-    k = (k0 / P.VS2) / ((float)n_c + 1e-8f);
-    bb = P.INV - (P.VS * k) / 2.0f;
-}
-
-// ---- the k == 0 time (u / fps) / 9 (LDATI.py:196) without the two IEEE division sequences ------------------------
-// Both divisors are constants of the call.  x / y = fma(fma(-q, y, x), r, q) with q = x * r, r = RN(1 / y), is the
-// correctly rounded quotient for all but rare (x, y); instead of proving which, the composition is checked against the
-// IEEE divisions for EVERY uniform the Philox path can produce (u = m * 2^-24, m < 2^24) by a 16 M-thread kernel, once
-// per device and FPS, enqueued in front of the first emit that needs it; the result lands in g_fastdiv[slot] and the
-// kernels take the fast form only when it says "identical for all inputs" (replayed uniforms are arbitrary floats: they
-// always take the divisions).  22 -> 6 VALU operations on a path every wave with a multi-event voxel executes.
-struct FastDiv { unsigned fps_bits; int ok; int tab_ready; int ok64; };
-__device__ FastDiv g_fastdiv[8];
-__device__ unsigned g_fastdiv_bad[8];
-__device__ unsigned g_fast64_bad[8];
-// The slope parameters {k, b} of a multi-event voxel (LDATI.py:188-190) depend on two small integers only -- the central
-// difference of the neighbouring counts and the voxel's own count -- and cost three IEEE divisions: tabulated once per
-// device and FPS by the very expressions of slope_params (so the entries ARE its results), looked up afterwards.
-__device__ float2 g_slope_tab[8][kSlopeTab];
-
-__device__ __forceinline__ float k0_time_fast(float u, float FPS, float RFPS, float R9) {
-    float q = u * RFPS;
-    q = __builtin_fmaf(__builtin_fmaf(-q, FPS, u), RFPS, q);
-    float t = q * R9;
-    t = __builtin_fmaf(__builtin_fmaf(-t, 9.0f, q), R9, t);
-    return t;
-}
-
-// ---- the single-event time (LDATI.py:156-165) without its two f64 division sequences ---------------------------------
-// t = (double)debt / fps / 9 with two constant divisors: q = x r, q = fma(fma(-q, y, x), r, q) with r = RN(1 / y) in f64, twice.
-// As for k0_time_fast the composition is CHECKED, not proven: a kernel compares it with the IEEE divisions for every f32 the
-// tendency of a forward-relocated voxel can take -- all floats in [0, 1) and all negative ones down to -2^-18 (the
-// recurrence leaves debt in (-1e-6 - ulp, 1)) -- once per device and fps (~2e9 values, a few ms); the kernels use it only when
-// the verdict is "identical everywhere" AND the lane's value lies inside the checked range (anything else -- the
-// bidirectional branch's tendencies reach 2 -- takes the divisions).  ~70 -> ~12 f64 operations per single event, which is
-// most events of real UNet output.
-__device__ __forceinline__ double single_time_fast(float debt, double fps, double rfps, double r9) {
-    const double x = (double)debt;
-    double q = x * rfps;
-    q = __builtin_fma(__builtin_fma(-q, fps, x), rfps, q);
-    double t = q * r9;
-    t = __builtin_fma(__builtin_fma(-t, 9.0, q), r9, t);
-    return t;
-}
-constexpr unsigned kFast64Neg = 0x36800000u;                 // bits of 2^-18: negative tendencies checked down to -2^-18
-__device__ __forceinline__ bool single_fast_range(float debt) { return debt < 1.0f && debt > -0x1p-18f; }
-
-__global__ __launch_bounds__(256) void ldati_fast64_check_kernel(double fps, double rfps, double r9, int slot) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
-    const unsigned npos = 0x3F800000u;                                    // floats in [0, 1)
-    if (i >= (unsigned long long)npos + kFast64Neg) return;
-    const unsigned bits = i < npos ? (unsigned)i : 0x80000000u + (unsigned)(i - npos);
-    const float d = __uint_as_float(bits);
-    const double want = (double)d / fps / 9.0;
-    const double got = single_time_fast(d, fps, rfps, r9);
-    if (!(want == got)) atomicAdd(&g_fast64_bad[slot], 1u);      // (numeric: -0 against +0 for debt = -0 is the same time)
-}
-
-__global__ __launch_bounds__(256) void ldati_fastdiv_check_kernel(float FPS, float RFPS, float R9, int slot) {
-    const unsigned m = blockIdx.x * 256u + threadIdx.x;                  // < 2^24
-    const float u = (float)m * (1.0f / 16777216.0f);
-    const float want = (u / FPS) / 9.0f;
-    const float got = k0_time_fast(u, FPS, RFPS, R9);
-    if (__float_as_uint(want) != __float_as_uint(got)) atomicAdd(&g_fastdiv_bad[slot], 1u);
-}
-__global__ __launch_bounds__(256) void ldati_slope_tab_kernel(float VS, float VS2, float INV, int slot) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= kSlopeTab) return;
-    const int d = i / (kSlopeM + 1) - kSlopeM, n = i % (kSlopeM + 1);
-    const float sxy = (float)d;                                // = (float)n_r - (float)n_l: small integers, exact
-    const float k0 = (3.0f * sxy) / 6.0f;
-    const float k = (k0 / VS2) / ((float)n + 1e-8f);
-    g_slope_tab[slot][i] = make_float2(k, INV - (VS * k) / 2.0f);
-}
-__global__ void ldati_fastdiv_commit_kernel(float FPS, int slot) {
-    g_fastdiv[slot].fps_bits = __float_as_uint(FPS);
-    g_fastdiv[slot].ok = g_fastdiv_bad[slot] == 0u ? 1 : 0;
-    g_fastdiv[slot].ok64 = g_fast64_bad[slot] == 0u ? 1 : 0;
-    g_fastdiv[slot].tab_ready = 1;
-}
-
-// multi-event timestamp, all f32 (LDATI.py:195-196,210-212)
-__device__ __forceinline__ long long multi_ts(float k, float bb, float u, float offt,
-                                              const LdatiParams &P) {
-    float t;
-    if (P.strategy == V2CE_STRATEGY_RANDOM) {
-        t = u;                                    // LDATI.py:173-174: the raw uniform, in seconds
-    } else if (k == 0.0f) {
-        t = (u / P.FPS) / 9.0f;
-    } else {
-        const float s = bb * bb + (2.0f * k) * u;
-        t = (-bb + __builtin_sqrtf(s)) / k;
-    }
-    t = t + offt;
-    t = t * 1e6f;
-    return (long long)t;
-}
-
-// the same, f32 -> i32 (bit-identical to the i64 conversion while |t| < 2^31: P.ts32) and the key
-__device__ __forceinline__ unsigned multi_key(float k, float bb, float u, float offt, int kbase32, const LdatiParams &P,
-                                              bool fast = false) {
-    float t;
-    if (P.strategy == V2CE_STRATEGY_RANDOM) {
-        t = u;
-    } else if (k == 0.0f) {
-        t = fast ? k0_time_fast(u, P.FPS, P.RFPS, P.R9) : (u / P.FPS) / 9.0f;
-    } else {
-        const float s = bb * bb + (2.0f * k) * u;
-        t = (-bb + __builtin_sqrtf(s)) / k;
-    }
-    t = t + offt;
-    t = t * 1e6f;
-    int key = (int)t - kbase32;
-    key = key < 0 ? 0 : key;
-    key = key >= P.NK ? P.NK - 1 : key;
-    return (unsigned)key;
-}
-
-__device__ __forceinline__ int key_of(long long T, long long kbase, int NK) {
-    long long k = T - kbase;
-    k = k < 0 ? 0 : k;
-    k = k >= NK ? NK - 1 : k;
-    return (int)k;
-}
-
-// Bidirectional relocation (LDATI.py:107-122) gets a key window sized for NON-NEGATIVE voxels (host_scalars): a negative voxel can
-// carry a tendency further out (bin 8's is y[9] itself).  The kernel instances that serve bidirectional calls take their keys
-// from here: the same key, and kStatusKeyWindow in the call's status word when the time lies outside [kbase, kbase + NK) --
-// the clamp would otherwise move the event's timestamp silently.  Forward calls never reach the clamp (the debt stays in
-// (-2e-6, 1), multi-event times in their bin) and keep key_of / multi_key / single_key.
-constexpr unsigned kStatusKeyWindow = 4u;
-__device__ __forceinline__ int key_of_reporting(bool has, long long T, long long kbase, int NK, int *status) {
-    const long long k = T - kbase;
-    if (has && (k < 0 || k >= NK)) atomicOr(reinterpret_cast<unsigned *>(status), kStatusKeyWindow);
-    return key_of(T, kbase, NK);
-}
-
-// the key of a single event: fast form when the wave's tendencies all lie inside the checked range (`fast`: the device
-// verdict, 32-bit times), else the divisions.  Must be called by whole waves (the range test is a wave vote).
-__device__ __forceinline__ unsigned single_key(bool has, float debt, float offt, long long kbase, bool fast, const LdatiParams &P) {
-    const bool in = !has || single_fast_range(debt);
-    if (fast && __ballot(!in) == 0ull) {
-        double t = single_time_fast(debt, P.fps, P.RFPS64, P.R9_64);
-        t += (double)offt;
-        t *= 1e6;
-        int k = (int)t - (int)kbase;                      // (int)t == (long long)t while |t| < 2^31 (P.ts32)
-        k = k < 0 ? 0 : k;
-        return (unsigned)(k >= P.NK ? P.NK - 1 : k);
-    }
-    return (unsigned)key_of(single_ts(debt, P.fps, offt), kbase, P.NK);
-}
-
-
-// ballot match-any: lanes of `has_mask` with equal `key` form a peer group.  Returns the rank of
-// this lane inside its group (peers on lower lanes) and the group size.  ~5 VALU per key bit.
-__device__ __forceinline__ unsigned match_rank(unsigned key, int nbits, unsigned long long has_mask,
-                                               unsigned &npeers) {
-    unsigned mlo = 0, mhi = 0;                           // lanes that differ from this lane in some bit
-    for (int b = 0; b < nbits; ++b) {
-        const int sel = __builtin_amdgcn_sbfe((int)key, b, 1);          // 0 or -1
-        const unsigned long long m = __ballot(sel != 0);
-        mlo |= (unsigned)m ^ (unsigned)sel;
-        mhi |= (unsigned)(m >> 32) ^ (unsigned)sel;
-    }
-    const unsigned plo = (unsigned)has_mask & ~mlo, phi = (unsigned)(has_mask >> 32) & ~mhi;
-    npeers = (unsigned)__popc(plo) + (unsigned)__popc(phi);
-    return __builtin_amdgcn_mbcnt_hi(phi, __builtin_amdgcn_mbcnt_lo(plo, 0u));
-}
-
-// One 64-record batch of a stable counting sort: `slot` = this wave's running base of the lane's
-// bin (LDS, owned by the wave).  Returns base + rank; the last peer advances the base.
-__device__ __forceinline__ unsigned take_slots(bool has, unsigned key, int nbits, unsigned *slot) {
-    unsigned npeers;
-    const unsigned rank = match_rank(key, nbits, __ballot(has), npeers);
-    unsigned pos = 0;
-    if (has) {
-        const unsigned base = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        __builtin_amdgcn_wave_barrier();
-        if (rank + 1 == npeers) __hip_atomic_store(slot, base + npeers, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        pos = base + rank;
-    }
-    __builtin_amdgcn_wave_barrier();
-    return pos;
-}
-
-// The same on a histogram that packs the counters of TWO waves into one word (16 bits each, `sh` = 0 or 16: the tile
-// pass): the word is shared with the neighbouring wave, so the group's slots are taken with one atomic add by its first
-// lane and handed to the peers through the LDS crossbar.
-__device__ __forceinline__ unsigned take_slots_packed(bool has, unsigned key, int nbits, unsigned *slot, unsigned sh) {
-    unsigned mlo = 0, mhi = 0;
-    const unsigned long long has_mask = __ballot(has);
-    for (int b = 0; b < nbits; ++b) {
-        const int sel = __builtin_amdgcn_sbfe((int)key, b, 1);
-        const unsigned long long m = __ballot(sel != 0);
-        mlo |= (unsigned)m ^ (unsigned)sel;
-        mhi |= (unsigned)(m >> 32) ^ (unsigned)sel;
-    }
-    const unsigned plo = (unsigned)has_mask & ~mlo, phi = (unsigned)(has_mask >> 32) & ~mhi;
-    const unsigned npeers = (unsigned)__popc(plo) + (unsigned)__popc(phi);
-    const unsigned rank = __builtin_amdgcn_mbcnt_hi(phi, __builtin_amdgcn_mbcnt_lo(plo, 0u));
-    const int leader = plo ? __builtin_ctz(plo) : 32 + __builtin_ctz(phi | 0x80000000u);
-    unsigned old = 0;
-    if (has && rank == 0) old = atomicAdd(slot, npeers << sh);
-    old = (unsigned)__shfl((int)old, leader);
-    return ((old >> sh) & 0xFFFFu) + rank;
-}
-
-// ---- ranks straight from LDS atomics ------------------------------------------------------------
-// On gfx950 one wave-instruction of ds_add_rtn_u32 serves the lanes that hit the same LDS word in
-// ascending lane order (tools/micro/lds_atomic_order.hip: 0 exceptions in 5.4e9 returned values),
-// so the returned value IS the stable rank and the ballot match-any (~4 VALU per key bit and batch)
-// is not needed.  That order is not an architectural promise: a probe kernel checks it on every
-// device the library runs on (enqueued once, in front of the first count call) and only then sets
-// g_lds_order_ok; until / unless it does, the kernels use the ballot ranks (identical results).
-__device__ int g_lds_order_ok = 0;
-__device__ unsigned g_lds_probe_bad = 0, g_lds_probe_done = 0;
-
-// ---- in-kernel phase stamps (diagnostic build only: make STAMP=1) ---------------------------------
-#ifdef V2CE_STAMP
-__device__ unsigned long long g_stamp[32];
-#define STAMP_DECL unsigned long long st_last = __builtin_amdgcn_s_memtime(), st_acc[12] = {0}
-#define STAMP(i) do { const unsigned long long st_now = __builtin_amdgcn_s_memtime(); st_acc[i] += st_now - st_last; st_last = st_now; } while (0)
-#define STAMP_FLUSH(base, n) do { if (threadIdx.x == 0) for (int st_i = 0; st_i < (n); ++st_i) atomicAdd(&g_stamp[(base) + st_i], st_acc[st_i]); } while (0)
-#else
-#define STAMP_DECL
-#define STAMP(i)
-#define STAMP_FLUSH(base, n)
-#endif
-
-__global__ __launch_bounds__(256) void ldati_lds_order_probe_kernel(int iters) {
-    __shared__ unsigned tab[4][512];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    unsigned s = (blockIdx.x * 256 + threadIdx.x) * 2654435761u + 12345u;
-    unsigned nbad = 0;
-    for (int it = 0; it < iters; ++it) {
-        for (int i = lane; i < 512; i += 64) tab[wid][i] = 7u * i;
-        __builtin_amdgcn_wave_barrier();
-        s = s * 1664525u + 1013904223u;
-        const unsigned range = 1u << (it % 10);
-        const unsigned key = (s >> 9) & (range - 1u);
-        const bool act = ((s >> 5) & 7u) != 0u || (it & 1);
-        unsigned got = 0;
-        if (act) got = atomicAdd(&tab[wid][key], 1u);
-        unsigned np;
-        const unsigned want = 7u * key + match_rank(key, 9, __ballot(act), np);
-        if (act && got != want) ++nbad;
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (nbad) atomicAdd(&g_lds_probe_bad, nbad);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        const unsigned done = atomicAdd(&g_lds_probe_done, 1u);
-        if (done == gridDim.x - 1) {
-            __threadfence();
-            g_lds_order_ok = atomicAdd(&g_lds_probe_bad, 0u) == 0u ? 1 : 0;
-        }
-    }
-}
-
-// slot of one record in a stable counting sort batch: LDS-atomic rank when the device passed the
-// probe, ballot rank otherwise
-__device__ __forceinline__ unsigned take_slot(bool atomic_order, bool has, unsigned key, int nbits, unsigned *slot) {
-    if (atomic_order) return has ? atomicAdd(slot, 1u) : 0u;
-    return take_slots(has, key, nbits, slot);
-}
-
-// px / W for px + 0.5 < 2^22 in three operations: (px + 0.5) / W lies at least 0.5 / W away from every integer, and the
-// two roundings (1 / W, the product) move it by less than (px + 0.5) / W * 2^-23 < 0.5 / W, so the truncation is exact
-__device__ __forceinline__ unsigned div_tiny(unsigned px, float rcpW) {
-    return (unsigned)(((float)px + 0.5f) * rcpW);
-}
-
-// px / W for px < 2^24 (exact in f32) without an integer division
-__device__ __forceinline__ unsigned div_small(unsigned px, unsigned W, float rcpW) {
-    unsigned q = (unsigned)((float)px * rcpW);
-    const int r = (int)(px - q * W);
-    q += (r >= (int)W) ? 1u : 0u;
-    q -= (r < 0) ? 1u : 0u;
-    return q;
-}
-
-__device__ __forceinline__ void store_packed_bytes(unsigned char *dst, long long t, unsigned xx,
-                                                   unsigned yy, unsigned pp) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) dst[k] = (unsigned char)((unsigned long long)t >> (8 * k));
-    dst[8] = (unsigned char)xx; dst[9] = (unsigned char)(xx >> 8);
-    dst[10] = (unsigned char)yy; dst[11] = (unsigned char)(yy >> 8);
-    dst[12] = (unsigned char)pp;
-}
-
-// inclusive scan over the 64 lanes of a wave: DPP row shifts inside the rows of 16 lanes, then the two row
-// broadcasts of gfx9 (lane 15 of a row into the next row; lane 31 into rows 2-3) -- six VALU operations instead
-// of six dependent ds_bpermute round trips through the LDS crossbar (~100 cycles each)
-__device__ __forceinline__ unsigned wave_incl_scan(unsigned v, int lane) {
-    (void)lane;
-    int x = (int)v;
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);   // row_shr:1
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);   // row_shr:2
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);   // row_shr:4
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);   // row_shr:8
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
-    return (unsigned)x;
-}
-
-// exclusive scan of one value per thread over a workgroup of NW <= 64 waves; `part` = NW LDS words.
-// Returns the exclusive prefix; *total = sum over the workgroup.  ONE barrier: every wave scans the NW wave totals itself
-// (a 64-lane DPP scan costs less than a second barrier and a serial loop on one thread).  The caller separates two scans
-// that share `part` by a barrier of its own (every call site has one: the totals are read right behind the barrier here).
-template <int NW>
-__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned *part, unsigned *total) {
-    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const unsigned incl = wave_incl_scan(v, lane);
-    if (lane == 63) part[wid] = incl;
-    __syncthreads();
-    const unsigned pin = wave_incl_scan(lane < NW ? part[lane] : 0u, lane);
-    *total = (unsigned)__builtin_amdgcn_readlane((int)pin, NW - 1);
-    const unsigned base = wid ? (unsigned)__builtin_amdgcn_readlane((int)pin, wid - 1) : 0u;
-    return base + incl - v;
-}
-
-// the same for two values per thread with one barrier; `part` = 2 * NW LDS words
-template <int NW>
-__device__ __forceinline__ void block_excl_scan2(unsigned a, unsigned e, unsigned *part, unsigned &a_ex,
-                                                 unsigned &e_ex, unsigned &a_tot, unsigned &e_tot) {
-    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const unsigned ia = wave_incl_scan(a, lane), ie = wave_incl_scan(e, lane);
-    if (lane == 63) { part[wid] = ia; part[NW + wid] = ie; }
-    __syncthreads();
-    const unsigned pa = wave_incl_scan(lane < NW ? part[lane] : 0u, lane);
-    const unsigned pe = wave_incl_scan(lane < NW ? part[NW + lane] : 0u, lane);
-    a_tot = (unsigned)__builtin_amdgcn_readlane((int)pa, NW - 1);
-    e_tot = (unsigned)__builtin_amdgcn_readlane((int)pe, NW - 1);
-    a_ex = (wid ? (unsigned)__builtin_amdgcn_readlane((int)pa, wid - 1) : 0u) + ia - a;
-    e_ex = (wid ? (unsigned)__builtin_amdgcn_readlane((int)pe, wid - 1) : 0u) + ie - e;
-}
-
-// `want` consecutive slots of an LDS counter for every lane with ONE atomic per wave (all 64 lanes must be active):
-// a per-lane atomicAdd on one address is served lane by lane -- up to 64 LDS cycles per wave instruction.
-__device__ __forceinline__ unsigned wave_alloc(unsigned *counter, unsigned want, int lane) {
-    const unsigned incl = wave_incl_scan(want, lane);
-    const unsigned tot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
-    unsigned base = 0;
-    if (tot) {                                              // wave-uniform
-        if (lane == 63) base = atomicAdd(counter, tot);
-        base = (unsigned)__builtin_amdgcn_readlane((int)base, 63);
-    }
-    return base + incl - want;
-}
 
 // ---------------------------------------------------------------------------------------------
 // count: workgroup per (frame, tile); events per (tile, bin); max count per voxel
@@ -2913,163 +2348,18 @@ __global__ void zero_words_kernel(unsigned *a, int na, unsigned *b, int nb) {
     if (b && i < nb) b[i] = 0u;
 }
 
-// host-side scalars, computed exactly like CPU torch does
-struct HostScalars {
-    float VS, VS2, INV, FPS;
-    float offt[9];
-    long long kbase[9];
-    long long NK;
-    int nbits;
-    size_t lds_bytes;     // of the sweep kernel
-    bool sweep_ok;        // 4*NK counters fit the LDS
-    bool ok;
-};
-
-HostScalars host_scalars(double fps, double t0, bool bidir = false, bool random = false) {
-    HostScalars h{};
-    const double vs = 1.0 / fps / 9.0;
-    h.VS = (float)vs;
-    h.VS2 = (float)(vs * vs);
-    h.INV = (float)(1.0 / vs);
-    h.FPS = (float)fps;
-    for (int c = 0; c < 9; ++c) h.offt[c] = (float)(0.0 + (double)c * vs) + (float)t0;
-    // f32 resolution of (t + offt)*1e6 near the last bin decides how far a multi-event timestamp
-    // can round outside [offt, offt + vs]; size the slack from it.
-    const double top = (double)fabsf(h.offt[8]) + vs;
-    const double ulp_us = top * 1.1920929e-7 * 1e6;      // one f32 ulp of the largest time, in us
-    const long long slack = 16 + (long long)(8.0 * ulp_us);
-    const long long span = (long long)(vs * 1e6) + 2;
-    // forward relocation: every timestamp lies in its bin, whatever the (finite) voxel values.  Bidirectional
-    // (LDATI.py:107-122), NON-NEGATIVE voxels: a single event's tendency lies in (-1, 2) bin widths (bin 5: bless - debt;
-    // bin 8: y[9] < 2 when n == 1) -- one bin width before and one after.  With negative voxels no margin holds (bin 8's
-    // tendency is y[9] itself, and n == 1 only bounds y[8] + y[9]): the bidirectional kernel instances report a time
-    // outside the window in the status word (key_of_reporting) and the call is refused (DeviceEvents.check).
-    // 'random' (LDATI.py:173-174): the multi-event offsets are raw uniforms in SECONDS.
-    const long long before = bidir ? span : 0;
-    const long long after = (random ? 1000000 : 0) + (bidir ? span : 0);
-    const long long nk = before + span + after + 2 * slack;
-    for (int c = 0; c < 9; ++c) h.kbase[c] = (long long)((double)h.offt[c] * 1e6) - slack - before;
-    h.NK = nk;
-    // the two-level path's key range; the generic ('random') path only needs 20-bit keys
-    h.ok = nk > 0 && (random ? nk < (1ll << 20) : nk <= ((long long)kMaxNB << kMaxShift));
-    // sweep kernel: 4*NK*4 B must fit 160 KiB of LDS with the scratch beside it; forward relocation only
-    h.sweep_ok = nk > 0 && nk <= 9600 && !bidir && !random;
-    int nb = 0;
-    while ((1ll << nb) < nk) ++nb;
-    h.nbits = nb;
-    h.lds_bytes = (size_t)(4 * nk + 256) * 4 + 3 * 128 * 4;
-    return h;
-}
-
-// workgroup size of the tile pass: 1024 threads (2 pixels each) for dense tiles, whose LDS footprint
-// allows one workgroup per CU anyway; 512 threads (4 pixels each, half the barrier traffic and
-// histogram rows) for sparse ones.  V2CE_LDATI_TILE_THREADS = 512 | 1024 overrides (kernel A/B runs).
-int tile_threads_choice(int64_t max_tile_events) {
-    static const int v = [] {
-        const char *e = getenv("V2CE_LDATI_TILE_THREADS");
-        const int n = e ? atoi(e) : 0;
-        return n == 512 || n == 1024 ? n : 0;
-    }();
-    return v ? v : (max_tile_events > 4096 ? 1024 : 512);
-}
-
-// dynamic LDS of ldati_tile_dense_kernel<NW>: S [capA] | O [capA + 2] | hist [NW][NB] | wave totals, scan partials, batch counter
-size_t dense_tile_lds(int capA, int NB, int NW) {
-    return ((size_t)2 * capA + 8 + (size_t)NW * NB + 3 * NW + NW + 1 + 2 + 18 + 10 + 2) * 4;
-}
-
-// geometry and capacities of the two-level path
-struct Plan {
-    int tpp, T, Tp, shift, NB, nb1, PB, capA, cap2, tbits, tile_threads, span, sort_threads;
-    size_t n_tab, n_bkt;                 // entries of roff; of bofs
-    size_t lds_tile, lds_sort;
-    size_t bytes;                        // workspace
-    bool ok;
-};
-
-Plan make_plan(const HostScalars &h, int B, int H, int W, int64_t total_events,
-               int64_t max_segment_events, int64_t max_tile_events) {
-    Plan p{};
-    const long long HW = (long long)H * W;
-    p.tpp = (int)((HW + kTilePix - 1) / kTilePix);
-    p.T = 2 * p.tpp;
-    p.Tp = (p.T + 7) & ~7;
-    int pb = 1;
-    while ((1ll << pb) < HW) ++pb;
-    p.PB = pb;
-    // coarse (level 1) bucket width 2^shift us: at most 16 us, finer when the densest segment would
-    // put more than cap2/20 records into an AVERAGE bucket (on real UNet output the fullest bucket of a
-    // segment holds ~20x the average: timestamps crowd at the end of a bin), never finer than kMaxNB
-    // buckets allow.  The sort groups (bucket scan kernel) merge consecutive buckets up to cap2 records.
-    // sort workgroups of 128 threads (3072 records) for segments of real UNet output, 256 (6144) for dense ones: measured on the
-    // e2e step (densest segment 85 K events) 151 -> 98 us, sparse bench 93 -> 73 us, on the stress chunk 432 -> 490 us, pano sort
-    // -66 us but bucket scan +80 us (V2CE_LDATI_SORT_THREADS overrides; kernel A/B runs)
-    {
-        const char *e = getenv("V2CE_LDATI_SORT_THREADS");            // (read per plan: tests switch it inside one process)
-        const int ev = e ? atoi(e) : 0, forced = ev == 64 || ev == 128 || ev == 256 ? ev : 0;
-        // (the densest segment spread evenly over its keys: a group of kMaxSpanKeys keys then holds at most 1.5 x 3072 records --
-        // groups of such segments are closed by their key span, not by their record count)
-        p.sort_threads = forced ? forced : (max_segment_events * kMaxSpanKeys > 4608 * h.NK ? 256 : 128);
-    }
-    const int kSortThreads = max_segment_events > 2048 ? p.sort_threads : 256, kSortWaves = kSortThreads / 64;
-    p.sort_threads = kSortThreads;
-    p.cap2 = max_segment_events > 2048 ? kSortThreads * 24 : kSortThreads * 8;
-    int shift = 4;
-    while (shift > 0 && (double)max_segment_events * (double)(1 << shift) / (double)h.NK > p.cap2 / 20.0) --shift;
-    while (shift < kMaxShift && ((h.NK + (1ll << shift) - 1) >> shift) > kMaxNB) ++shift;
-    // Dense segments (the rule above asks for the finest buckets) gain nothing from more than ~256 buckets: the sort groups
-    // merge consecutive buckets up to cap2 records anyway, while the tile pass pays per (wave, bucket) cell and the gather per
-    // run (V2CE_LDATI_NB_SOFT overrides the soft limit; kernel A/B runs)
-    {
-        static const int soft = [] { const char *e = getenv("V2CE_LDATI_NB_SOFT"); const int v = e ? atoi(e) : 0; return v >= 16 && v <= kMaxNB ? v : kMaxNB; }();   // (measured: 256 = tile pass -36 us, sort +31 us, bucket scan +10 us on the stress chunk: off)
-        while (shift < 4 && ((h.NK + (1ll << shift) - 1) >> shift) > soft) ++shift;
-    }
-    p.shift = shift;
-    p.NB = (int)((h.NK + (1ll << shift) - 1) >> shift);
-    int nb1 = 0;
-    while ((1 << nb1) < p.NB) ++nb1;
-    p.nb1 = nb1;
-    // key span of a sort group: 128 keys for dense segments; for the small-group regime (128-thread workgroups) the groups are
-    // closed by their span, not by their records, so a wider span means fewer, fuller groups (V2CE_LDATI_SPAN_KEYS: A/B runs)
-    int span_keys = kMaxSpanKeys;
-    {
-        const char *e = getenv("V2CE_LDATI_SPAN_KEYS");
-        const int ev = e ? atoi(e) : 0;
-        if (ev == 128 || ev == 256 || ev == 512) span_keys = ev;
-        else if (p.sort_threads == 128 && max_segment_events > 2048) span_keys = kSmallGroupSpanKeys;
-    }
-    p.span = (span_keys >> shift) > 0 ? (span_keys >> shift) : 1;
-    p.tbits = 0;
-    while ((1 << p.tbits) < p.T) ++p.tbits;
-    p.capA = (int)((max_tile_events + 255) / 256 * 256);
-    if (p.capA < 256) p.capA = 256;
-    p.ok = h.ok && p.T <= kMaxTiles && p.NB <= kMaxNB && p.capA <= kCapTile &&
-           pb <= 22 && total_events < (1ll << 32) && B * 9 <= 65535;
-    p.n_bkt = (size_t)B * 9 * (size_t)(p.NB + 1);
-    p.n_tab = p.n_bkt * (size_t)p.T;
-    p.tile_threads = tile_threads_choice(max_tile_events);
-    p.lds_tile = (size_t)(2 * p.capA + 2048) * 4 + (size_t)kTilePix * 8 +
-                 (size_t)(p.tile_threads / 128) * p.NB * 4 + 2 * (p.tile_threads / 64 + 1) * 4;
-    const size_t bins = (size_t)4 * (size_t)(p.span << shift);          // <= 4 * max(kMaxSpanKeys, 2^shift)
-    const size_t hist_bins = bins > 4 * (size_t)kMaxSpanKeys ? bins : 4 * (size_t)kMaxSpanKeys;
-    const size_t tables = kSortWaves * hist_bins * 4 + (size_t)(2 * p.T) * 4 + (size_t)(2 * (p.cap2 / 32)) * 4 + (kSortWaves + 1) * 4;
-    const size_t stage = (size_t)kSortThreads * 13 * 4;
-    p.lds_sort = (size_t)(p.cap2 + 20) * 4 + (tables > stage ? tables : stage);
-    // bofs | groups [B*9*NB] | big_list [B*9*NB] | ngroups [B*9] | seg_flag [B*9] | status [4] (status, nbig) |
-    // records (u32) | roff (u16) | gruns (u32 [B*9][NB][Tp])
-    p.bytes = (p.n_bkt + 2 * (size_t)B * 9 * p.NB + 2 * (size_t)B * 9 + 4 +
-               (size_t)(total_events > 0 ? total_events : 0)) * 4 + ((p.n_tab * 2 + 3) / 4) * 4 + (size_t)B * 9 * p.NB * p.Tp * 4;
-    if (p.lds_tile > 160 * 1024 || p.lds_sort > 160 * 1024) p.ok = false;
-    return p;
-}
-
 }  // namespace
 }  // namespace v2ce
 
 using namespace v2ce;
 
 namespace {
-struct Opts { int strategy, bidir, pooling, pool_k; };
+// a failed launch would leave stale status words that the host then trusts: reported
+int zero_words(hipStream_t s, void *a, int na, void *b = nullptr, int nb = 0) {
+    hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, s, static_cast<unsigned *>(a), na, static_cast<unsigned *>(b), nb);
+    V2CE_HIP_CHECK(hipGetLastError());
+    return V2CE_OK;
+}
 
 int probe_lds_order(hipStream_t s) {   // once per device: check that LDS atomics return ranks in lane order (see g_lds_order_ok)
     static std::atomic<unsigned long long> probed{0};
@@ -3091,85 +2381,146 @@ int read_options(const v2ce_ldati_options *o, Opts &out, const char *who) {
     V2CE_REQUIRE(out.pooling == V2CE_POOL_NONE || out.pooling == V2CE_POOL_AVG || out.pooling == V2CE_POOL_WEIGHTED,
                  V2CE_ERR_BAD_ARG, "%s: bad pooling_type %d", who, out.pooling);
     V2CE_REQUIRE(out.pooling != V2CE_POOL_AVG || (out.pool_k >= 1 && out.pool_k <= 15 && (out.pool_k & 1)), V2CE_ERR_UNSUPPORTED,
-                 "%s: pooling_kernel_size %d (odd sizes 1..15: nn.AvgPool2d with padding k//2 keeps H x W only for odd k)",
-                 who, out.pool_k);
+                 "%s: pooling_kernel_size %d (odd sizes 1..15: nn.AvgPool2d with padding k//2 keeps H x W only for odd k)", who, out.pool_k);
     if (out.strategy != V2CE_STRATEGY_SLOPE) out.pooling = V2CE_POOL_NONE;      // pooling only shapes the slope (LDATI.py:175)
     return V2CE_OK;
 }
 
-// workspace of one emit call: the two-level part (or the generic part for 'random'), then the pooled
-// slope parameters
-struct Layout {
-    Plan plan;
-    bool generic;
-    size_t main_bytes, keys_bytes, sort_temp_bytes, soa_bytes, kbb_bytes, bytes;
-    bool ok;
-};
+// what the calls that compute timestamps say about time and the random draws
+struct DrawArgs { double fps; int rng_mode; const float *uniforms; int replay_max_n; uint64_t seed; int64_t frame_base; };
 
-Layout make_layout(const HostScalars &h, const Opts &o, int B, int H, int W, int64_t total, int64_t max_seg,
-                   int64_t max_tile, bool packed_out) {
-    Layout L{};
-    L.generic = o.strategy == V2CE_STRATEGY_RANDOM;
-    L.plan = make_plan(h, B, H, W, total, max_seg, max_tile);
-    const size_t n = (size_t)(total > 0 ? total : 0);
-    if (L.generic) {
-        // the tile pass still runs (in its key-writing mode): it needs the tile geometry and LDS plan
-        L.ok = h.ok && L.plan.T <= kMaxTiles && L.plan.capA <= kCapTile && L.plan.PB <= 22 && B * 9 <= 65535 &&
-               total < (1ll << 32) && L.plan.lds_tile <= 160 * 1024;
-        L.main_bytes = 16;                                            // status words
-        L.keys_bytes = 2 * ((n * 8 + 15) / 16) * 16;
-        size_t tb = 0;
-        if (n) (void)rocprim::radix_sort_keys(nullptr, tb, (unsigned long long *)nullptr, (unsigned long long *)nullptr, n, 0, 60);
-        L.sort_temp_bytes = (tb + 15) / 16 * 16;
-        L.soa_bytes = packed_out ? ((n * 13 + 15) / 16) * 16 + 64 : 0;
-    } else {
-        L.ok = L.plan.ok;
-        L.main_bytes = (L.plan.bytes + 15) / 16 * 16;
+// The argument checks count, count_fused and emit share.  frame_grid: the call launches a grid with one row per frame;
+// d: null for the count, which computes no timestamp.
+int check_call(const char *who, bool pointers, int B, int H, int W, bool frame_grid, const DrawArgs *d, const v2ce_ldati_options *options, Opts &o) {
+    V2CE_REQUIRE(pointers, V2CE_ERR_BAD_ARG, "%s: null pointer", who);
+    V2CE_REQUIRE(B > 0 && H > 0 && W > 0 && (long long)H * W < (1ll << 30), V2CE_ERR_BAD_ARG, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
+    V2CE_REQUIRE(W <= 32767 && H <= 32767, V2CE_ERR_UNSUPPORTED, "%s: x/y are int16 (LDATI.py:230-231)", who);
+    V2CE_REQUIRE(!frame_grid || B <= 65535, V2CE_ERR_UNSUPPORTED, "%s: B too large for one launch", who);
+    if (d) {
+        V2CE_REQUIRE(d->fps > 0, V2CE_ERR_BAD_ARG, "%s: fps must be positive", who);
+        V2CE_REQUIRE(d->rng_mode == V2CE_RNG_REPLAY || d->rng_mode == V2CE_RNG_PHILOX, V2CE_ERR_BAD_ARG, "%s: bad rng_mode %d", who, d->rng_mode);
+        V2CE_REQUIRE(d->rng_mode != V2CE_RNG_REPLAY || d->replay_max_n == 0 || d->uniforms != nullptr, V2CE_ERR_BAD_ARG, "%s: REPLAY mode needs the uniform tensor", who);
     }
-    L.kbb_bytes = o.pooling != V2CE_POOL_NONE ? (size_t)B * 2 * 9 * (size_t)H * W * 8 : 0;
-    L.bytes = L.main_bytes + L.keys_bytes + L.sort_temp_bytes + L.soa_bytes + L.kbb_bytes;
-    return L;
+    return read_options(options, o, who);
+}
+
+// the workspace of a call; the temporary size of the generic path's library radix sort is this file's to ask for
+TwoLevelWs workspace_of(const Plan &pl, const Opts &o, int B, int H, int W, int64_t total, bool packed_out) {
+    size_t tb = 0;
+    if (o.strategy == V2CE_STRATEGY_RANDOM && total > 0)
+        (void)rocprim::radix_sort_keys(nullptr, tb, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (size_t)total, 0, 60);
+    return two_level_ws(pl, o, B, H, W, total, packed_out, tb);
+}
+
+template <typename T>   // base + byte offset (the offsets of TileWs, TwoLevelWs, FusedLayout)
+T *at(const void *base, size_t offset) { return reinterpret_cast<T *>(static_cast<unsigned char *>(const_cast<void *>(base)) + offset); }
+void set_geometry(LdatiParams &P, const Plan &pl) {
+    P.shift = pl.shift; P.NB = pl.NB; P.nb1 = pl.nb1; P.T = pl.T; P.Tp = pl.Tp; P.tpp = pl.tpp; P.PB = pl.PB;
+}
+
+// once per device and FPS: the exhaustive check of k0_time_fast against the IEEE divisions (see g_fastdiv) and the table of slope parameters
+// (g_slope_tab), enqueued in front of the first call that uses them.  Seven slots per device (slot 7: v2ce_ldati_selfcheck's scratch); -1 = none left
+int fastdiv_slot(const HostScalars &h, const LdatiParams &P, hipStream_t st, int &slot) {
+    static std::mutex mu;
+    static unsigned seen[64][8];
+    static int n_seen[64];
+    slot = -1;
+    int dev = 0;
+    V2CE_HIP_CHECK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64) return V2CE_OK;
+    unsigned bits;
+    memcpy(&bits, &h.FPS, 4);
+    std::lock_guard<std::mutex> g(mu);
+    for (int i = 0; i < n_seen[dev]; ++i)
+        if (seen[dev][i] == bits) slot = i;
+    if (slot < 0 && n_seen[dev] < 7) {
+        slot = n_seen[dev]++;
+        seen[dev][slot] = bits;
+        hipLaunchKernelGGL(ldati_fastdiv_check_kernel, dim3(65536), dim3(256), 0, st, h.FPS, P.RFPS, P.R9, slot);
+        hipLaunchKernelGGL(ldati_fast64_check_kernel, dim3((0x3F800000u + kFast64Neg + 255u) / 256u), dim3(256), 0, st, P.fps, P.RFPS64, P.R9_64, slot);
+        hipLaunchKernelGGL(ldati_slope_tab_kernel, dim3((kSlopeTab + 255) / 256), dim3(256), 0, st, h.VS, h.VS2, h.INV, slot);
+        hipLaunchKernelGGL(ldati_fastdiv_commit_kernel, dim3(1), dim3(1), 0, st, h.FPS, slot);
+    }
+    return V2CE_OK;
+}
+
+int fill_params(LdatiParams &P, const HostScalars &h, const Opts &o, const Knobs &k, const float *vox, int B, int H, int W, const DrawArgs &d, hipStream_t st) {
+    P.vox = vox; P.B = B; P.H = H; P.W = W; P.HW = H * W;
+    P.fps = d.fps; P.VS = h.VS; P.VS2 = h.VS2; P.INV = h.INV; P.FPS = h.FPS;
+    for (int c = 0; c < 9; ++c) { P.offt[c] = h.offt[c]; P.kbase[c] = h.kbase[c]; }
+    P.NK = (int)h.NK; P.nbits = h.nbits;
+    P.ts32 = (fabs((double)h.offt[8]) + 1.0 + 1.0 / d.fps) * 1e6 < 2.0e9 ? 1 : 0;
+    P.strategy = o.strategy; P.bidir = o.bidir;
+    P.rng_mode = d.rng_mode; P.uniforms = d.uniforms; P.replay_max_n = d.replay_max_n;
+    P.seed = d.seed; P.frame_base = d.frame_base;
+    P.sweep_ok = h.sweep_ok ? 1 : 0;
+    P.RFPS = (float)(1.0 / (double)h.FPS); P.R9 = (float)(1.0 / 9.0);
+    P.RFPS64 = 1.0 / d.fps; P.R9_64 = 1.0 / 9.0;
+    P.fast_slot = -1;
+    if (o.strategy == V2CE_STRATEGY_SLOPE && !k.no_fastdiv)
+        if (int rc = fastdiv_slot(h, P, st, P.fast_slot)) return rc;
+    P.ballot_ranks = k.ballot_ranks ? 1 : 0;
+    return V2CE_OK;
+}
+
+CallFacts facts_of(const LdatiParams &P, const Opts &o, bool packed) { return CallFacts{o.pooling != V2CE_POOL_NONE, P.ts32 != 0, P.fast_slot >= 0, packed}; }
+
+// the tile pass of a call: the dense kernel, or the per-bin kernel for everything the dense one does not serve (choose_path)
+int launch_tile_pass(const LdatiParams &P, const Plan &pl, const PathChoice &c, hipStream_t st) {
+    if (c.dense_nw) {
+        auto dk = c.dense_nw == 8 ? ldati_tile_dense_kernel<8> : ldati_tile_dense_kernel<16>;
+        V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(dk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.dense_lds));
+        hipLaunchKernelGGL(dk, dim3(pl.T, P.B), dim3(64 * c.dense_nw), c.dense_lds, st, P);
+        return V2CE_OK;
+    }
+    auto tile_kernel = c.bidir ? (c.tile_threads == 512 ? ldati_tile_pass_kernel<512, 4, true> : ldati_tile_pass_kernel<1024, 2, true>)
+                               : (c.tile_threads == 512 ? ldati_tile_pass_kernel<512, 4, false> : ldati_tile_pass_kernel<1024, 2, false>);
+    V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_tile));
+    hipLaunchKernelGGL(tile_kernel, dim3(pl.T, P.B), dim3(c.tile_threads), pl.lds_tile, st, P);
+    return V2CE_OK;
+}
+
+template <bool FUSED>   // FUSED: v2ce_ldati_count_fused's form (counts the tiles as well, every tile's records into its own slot)
+int launch_sparse_pass(const LdatiParams &P, const Plan &pl, const PathChoice &c, hipStream_t st) {
+    auto sparse_kernel = c.bidir ? ldati_tile_sparse_kernel<FUSED, true> : ldati_tile_sparse_kernel<FUSED, false>;
+    V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(sparse_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSparseLds));
+    hipLaunchKernelGGL(sparse_kernel, dim3(pl.T, P.B), dim3(kSparseThreads), kSparseLds, st, P);
+    return V2CE_OK;
+}
+
+template <bool PACKED>
+auto sort_kernel_of(const PathChoice &c) -> void (*)(LdatiParams) {
+    if (c.sort_k == 8) return ldati_bucket_sort_kernel<PACKED, 8, 256>;
+    return c.sort_threads == 64 ? ldati_bucket_sort_kernel<PACKED, 24, 64>
+                                : c.sort_threads == 128 ? ldati_bucket_sort_kernel<PACKED, 24, 128> : ldati_bucket_sort_kernel<PACKED, 24, 256>;
+}
+
+// tile counts -> per-tile offsets, segment offsets and the statistics: the tail of both count calls
+int launch_count_scans(const TileWs &tw, void *tile_ws, int B, int64_t *seg_offsets, int64_t *stats, hipStream_t s) {
+    hipLaunchKernelGGL(ldati_tile_scan_kernel, dim3((B + 3) / 4), dim3(256), 0, s, at<unsigned>(tile_ws, tw.tc), B, (int)tw.T, at<unsigned>(tile_ws, tw.tile_off),
+                       at<unsigned>(tile_ws, tw.tile_src), (int)tw.Tp, reinterpret_cast<long long *>(seg_offsets), reinterpret_cast<unsigned long long *>(stats));
+    hipLaunchKernelGGL(ldati_seg_scan_kernel, dim3(1), dim3(256), 0, s, B * 9, reinterpret_cast<long long *>(seg_offsets), reinterpret_cast<unsigned long long *>(stats));
+    V2CE_HIP_CHECK(hipGetLastError());
+    return V2CE_OK;
 }
 }  // namespace
 
-extern "C" size_t v2ce_ldati_tile_ws_bytes(int B, int H, int W) {
-    if (B <= 0 || H <= 0 || W <= 0) return 0;
-    const long long tpp = ((long long)H * W + kTilePix - 1) / kTilePix;
-    const long long Tp = (2 * tpp + 7) & ~7ll;
-    return (size_t)2 * (size_t)B * (size_t)(2 * tpp) * 9 * 4 + (size_t)B * 9 * (size_t)Tp * 4;     // tile counts | tile offsets | the offsets [segment][tile]
-}
-
-extern "C" int v2ce_ldati_count(const float *vox, int B, int H, int W, const v2ce_ldati_options *options, void *tile_ws,
-                                size_t tile_ws_bytes, int64_t *seg_offsets, int64_t *stats,
-                                v2ce_stream_t stream) {
+extern "C" size_t v2ce_ldati_tile_ws_bytes(int B, int H, int W) { return B <= 0 || H <= 0 || W <= 0 ? 0 : tile_ws(B, H, W).bytes; }
+extern "C" int v2ce_ldati_count(const float *vox, int B, int H, int W, const v2ce_ldati_options *options, void *tile_ws_dev,
+                                size_t tile_ws_bytes, int64_t *seg_offsets, int64_t *stats, v2ce_stream_t stream) {
     clear_error();
-    V2CE_REQUIRE(vox && tile_ws && seg_offsets && stats, V2CE_ERR_BAD_ARG, "v2ce_ldati_count: null pointer");
-    V2CE_REQUIRE(B > 0 && H > 0 && W > 0 && (long long)H * W < (1ll << 30), V2CE_ERR_BAD_ARG,
-                 "v2ce_ldati_count: bad shape B=%d H=%d W=%d", B, H, W);
-    V2CE_REQUIRE(W <= 32767 && H <= 32767, V2CE_ERR_UNSUPPORTED,
-                 "v2ce_ldati_count: x/y are int16 (LDATI.py:230-231)");
-    V2CE_REQUIRE(B <= 65535, V2CE_ERR_UNSUPPORTED, "v2ce_ldati_count: B too large for one launch");
     Opts o;
-    if (int rc = read_options(options, o, "v2ce_ldati_count")) return rc;
-    V2CE_REQUIRE(tile_ws_bytes >= v2ce_ldati_tile_ws_bytes(B, H, W), V2CE_ERR_WORKSPACE,
-                 "v2ce_ldati_count: tile workspace %zu < %zu", tile_ws_bytes, v2ce_ldati_tile_ws_bytes(B, H, W));
+    if (int rc = check_call("v2ce_ldati_count", vox && tile_ws_dev && seg_offsets && stats, B, H, W, true, nullptr, options, o)) return rc;
+    const TileWs tw = tile_ws(B, H, W);
+    V2CE_REQUIRE(tile_ws_bytes >= tw.bytes, V2CE_ERR_WORKSPACE, "v2ce_ldati_count: tile workspace %zu < %zu", tile_ws_bytes, tw.bytes);
     hipStream_t s = as_stream(stream);
-    const int HW = H * W;
-    const int tpp = (HW + kTilePix - 1) / kTilePix, T = 2 * tpp;
-    unsigned *tc = static_cast<unsigned *>(tile_ws);
-    unsigned *tile_off = tc + (size_t)B * T * 9;
     if (int rc = probe_lds_order(s)) return rc;
-    hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<unsigned *>(stats), 8, static_cast<unsigned *>(nullptr), 0);
+    if (int rc = zero_words(s, stats, 8)) return rc;
     // 'random' emits like 'slope' (every draw of a multi-event voxel); 'none' only the singles
     const int count_strategy = o.strategy == V2CE_STRATEGY_NONE ? V2CE_STRATEGY_NONE : V2CE_STRATEGY_SLOPE;
-    hipLaunchKernelGGL(ldati_count_tiles_kernel, dim3(T, B), dim3(kCountThreads), 0, s, vox, HW, tpp, count_strategy, o.bidir, tc,
+    hipLaunchKernelGGL(ldati_count_tiles_kernel, dim3((unsigned)tw.T, B), dim3(kCountThreads), 0, s, vox, H * W, (int)tw.tpp, count_strategy, o.bidir, at<unsigned>(tile_ws_dev, tw.tc),
                        reinterpret_cast<unsigned long long *>(stats));
-    hipLaunchKernelGGL(ldati_tile_scan_kernel, dim3((B + 3) / 4), dim3(256), 0, s, tc, B, T, tile_off, tile_off + (size_t)B * T * 9, (T + 7) & ~7,
-                       reinterpret_cast<long long *>(seg_offsets), reinterpret_cast<unsigned long long *>(stats));
-    hipLaunchKernelGGL(ldati_seg_scan_kernel, dim3(1), dim3(256), 0, s, B * 9, reinterpret_cast<long long *>(seg_offsets),
-                       reinterpret_cast<unsigned long long *>(stats));
-    V2CE_HIP_CHECK(hipGetLastError());
-    return V2CE_OK;
+    return launch_count_scans(tw, tile_ws_dev, B, seg_offsets, stats, s);
 }
 
 extern "C" size_t v2ce_ldati_lds_bytes(double fps, double t0) {
@@ -3179,114 +2530,15 @@ extern "C" size_t v2ce_ldati_lds_bytes(double fps, double t0) {
 }
 
 extern "C" size_t v2ce_ldati_workspace_bytes(int B, int H, int W, double fps, double t0, const v2ce_ldati_options *options,
-                                             int64_t total_events, int64_t max_segment_events,
-                                             int64_t max_tile_events, int packed_output) {
+                                             int64_t total_events, int64_t max_segment_events, int64_t max_tile_events, int packed_output) {
     if (!(fps > 0) || B <= 0 || H <= 0 || W <= 0) return 0;
     Opts o;
     if (read_options(options, o, "v2ce_ldati_workspace_bytes")) return 0;
     const HostScalars h = host_scalars(fps, t0, o.bidir, o.strategy == V2CE_STRATEGY_RANDOM);
-    const Layout L = make_layout(h, o, B, H, W, total_events, max_segment_events, max_tile_events, packed_output != 0);
-    return L.ok ? L.bytes : 0;
+    const Plan pl = make_plan(h, read_knobs(), B, H, W, total_events, max_segment_events, max_tile_events);
+    const TwoLevelWs w = workspace_of(pl, o, B, H, W, total_events, packed_output != 0);
+    return w.ok ? w.bytes : 0;
 }
-
-namespace {
-// ---- fused count + sparse tile pass: geometry the kernel assumes BEFORE the counts exist, and its workspace ----------
-// The coarse-bucket geometry of a call follows from its densest segment (make_plan).  The fused kernel runs before that is
-// known, with the geometry of the caller's HINT (the previous call's max_segment_events: consecutive batches of a clip
-// agree); v2ce_ldati_emit_fused uses its records only if the plan made from the real counts has the same geometry and no
-// tile exceeded its slot.
-struct FusedLayout {
-    Plan p0;
-    size_t off_abs, off_rec, off_roff, bytes;
-    int slot_cap;                        // dense mode: records per (tile, bin) slot (= the tile pass's LDS capacity); 0 = sparse mode
-    bool ok;
-};
-// tile_bin_hint = 0: the sparse kernel's fused form (a slot of kSparseCap records per tile);  > 0: the dense kernel's (a slot per
-// (tile, bin), sized from the caller's expectation of the densest one)
-FusedLayout make_fused_layout(const HostScalars &h, const Opts &o, int B, int H, int W, int64_t seg_hint, int64_t tile_bin_hint = 0) {
-    FusedLayout F{};
-    F.p0 = make_plan(h, B, H, W, 0, seg_hint > 0 ? seg_hint : 0, tile_bin_hint > 0 ? tile_bin_hint : 0);
-    const Plan &p = F.p0;
-    F.slot_cap = tile_bin_hint > 0 ? p.capA : 0;
-    const size_t n_abs = (size_t)B * 9 * p.Tp, n_rec = F.slot_cap ? (size_t)B * p.T * 9 * (size_t)F.slot_cap : (size_t)B * p.T * kSparseCap;
-    F.ok = h.ok && p.T <= kMaxTiles && p.NB <= kMaxNB && p.PB <= 22 && B * 9 <= 65535 && n_rec < (1ull << 32) &&
-           (F.slot_cap ? (p.capA <= kCapTile && !o.bidir && dense_tile_lds(p.capA, p.NB, 16) <= 160 * 1024 && !getenv("V2CE_LDATI_OLD_TILE") &&
-                          n_rec <= (1ull << 30))                 // (at most 4 GiB of slots: beyond that the count pass is the cheaper price)
-                       : 9ll * ((long long)p.NB << p.shift) < (1ll << 20) && !getenv("V2CE_LDATI_NO_SPARSE")) &&
-           (o.strategy == V2CE_STRATEGY_SLOPE || o.strategy == V2CE_STRATEGY_NONE) && o.pooling == V2CE_POOL_NONE &&
-           !getenv("V2CE_LDATI_NO_FUSED");
-    F.off_abs = 16;
-    F.off_rec = (F.off_abs + n_abs * 4 + 15) / 16 * 16;
-    F.off_roff = (F.off_rec + n_rec * 4 + 15) / 16 * 16;
-    F.bytes = (F.off_roff + p.n_tab * 2 + 15) / 16 * 16;
-    return F;
-}
-
-int fill_params(LdatiParams &P, const HostScalars &h, const Opts &o, const float *vox, int B, int H, int W, double fps,
-                int rng_mode, const float *uniforms, int replay_max_n, uint64_t seed, int64_t frame_base, hipStream_t st) {
-    P.vox = vox; P.B = B; P.H = H; P.W = W; P.HW = H * W;
-    P.fps = fps; P.VS = h.VS; P.VS2 = h.VS2; P.INV = h.INV; P.FPS = h.FPS;
-    for (int c = 0; c < 9; ++c) { P.offt[c] = h.offt[c]; P.kbase[c] = h.kbase[c]; }
-    P.NK = (int)h.NK; P.nbits = h.nbits;
-    P.ts32 = (fabs((double)h.offt[8]) + 1.0 + 1.0 / fps) * 1e6 < 2.0e9 ? 1 : 0;
-    P.strategy = o.strategy; P.bidir = o.bidir;
-    P.rng_mode = rng_mode; P.uniforms = uniforms; P.replay_max_n = replay_max_n;
-    P.seed = seed; P.frame_base = frame_base;
-    P.sweep_ok = h.sweep_ok ? 1 : 0;
-    P.RFPS = (float)(1.0 / (double)h.FPS); P.R9 = (float)(1.0 / 9.0);
-    P.RFPS64 = 1.0 / fps; P.R9_64 = 1.0 / 9.0;
-    P.fast_slot = -1;
-    if (o.strategy == V2CE_STRATEGY_SLOPE && !getenv("V2CE_LDATI_NO_FASTDIV")) {
-        // once per device and FPS: the exhaustive check of k0_time_fast against the IEEE divisions (see g_fastdiv) and the
-        // table of slope parameters (g_slope_tab)
-        static std::mutex mu;
-        static unsigned seen[64][8];
-        static int n_seen[64];
-        int dev = 0;
-        V2CE_HIP_CHECK(hipGetDevice(&dev));
-        unsigned bits;
-        memcpy(&bits, &h.FPS, 4);
-        std::lock_guard<std::mutex> g(mu);
-        if (dev >= 0 && dev < 64) {
-            int slot = -1;
-            for (int i = 0; i < n_seen[dev]; ++i)
-                if (seen[dev][i] == bits) slot = i;
-            if (slot < 0 && n_seen[dev] < 7) {                   // (slot 7: v2ce_ldati_selfcheck's scratch)
-                slot = n_seen[dev]++;
-                seen[dev][slot] = bits;
-                hipLaunchKernelGGL(ldati_fastdiv_check_kernel, dim3(65536), dim3(256), 0, st, h.FPS, P.RFPS, P.R9, slot);
-                hipLaunchKernelGGL(ldati_fast64_check_kernel, dim3((0x3F800000u + kFast64Neg + 255u) / 256u), dim3(256), 0, st, fps, P.RFPS64,
-                                   P.R9_64, slot);
-                hipLaunchKernelGGL(ldati_slope_tab_kernel, dim3((kSlopeTab + 255) / 256), dim3(256), 0, st, h.VS, h.VS2, h.INV, slot);
-                hipLaunchKernelGGL(ldati_fastdiv_commit_kernel, dim3(1), dim3(1), 0, st, h.FPS, slot);
-            }
-            P.fast_slot = slot;
-        }
-    }
-    { const char *e = getenv("V2CE_LDATI_NO_ATOMIC_ORDER"); P.ballot_ranks = (e && e[0] == '1') ? 1 : 0; }
-    return V2CE_OK;
-}
-
-}  // namespace
-
-namespace {
-// the round-4 dense tile kernel serves the common call (forward relocation, 'slope' with the device tables of this fps or 'none',
-// no pooling, 32-bit times); everything else stays on the per-bin kernel
-bool dense_kernel_serves(const LdatiParams &P, const Opts &o) {
-    return !o.bidir && !P.kbb && P.ts32 && !getenv("V2CE_LDATI_OLD_TILE") &&
-           (o.strategy == V2CE_STRATEGY_NONE || (o.strategy == V2CE_STRATEGY_SLOPE && P.fast_slot >= 0));
-}
-int launch_dense_kernel(const LdatiParams &P, const Plan &pl, int B, hipStream_t st) {
-    const size_t lds8 = dense_tile_lds(pl.capA, pl.NB, 8), lds16 = dense_tile_lds(pl.capA, pl.NB, 16);
-    static const int force_nw = [] { const char *e = getenv("V2CE_LDATI_DENSE_NW"); return e ? atoi(e) : 0; }();   // kernel A/B runs
-    const bool w8 = force_nw == 16 ? false : (force_nw == 8 && lds8 <= 160 * 1024) ? true : lds8 <= 80 * 1024;       // two workgroups per CU
-    auto dk = w8 ? ldati_tile_dense_kernel<8> : ldati_tile_dense_kernel<16>;
-    const size_t lds = w8 ? lds8 : lds16;
-    V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(dk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(dk, dim3(pl.T, B), dim3(w8 ? 512 : 1024), lds, st, P);
-    return V2CE_OK;
-}
-}  // namespace
 
 extern "C" size_t v2ce_ldati_fused_ws_bytes(int B, int H, int W, double fps, double t0, const v2ce_ldati_options *options,
                                             int64_t expected_max_segment_events, int64_t expected_max_tile_bin_events) {
@@ -3294,289 +2546,200 @@ extern "C" size_t v2ce_ldati_fused_ws_bytes(int B, int H, int W, double fps, dou
     Opts o;
     if (read_options(options, o, "v2ce_ldati_fused_ws_bytes")) return 0;
     const HostScalars h = host_scalars(fps, t0, o.bidir, o.strategy == V2CE_STRATEGY_RANDOM);
-    const FusedLayout F = make_fused_layout(h, o, B, H, W, expected_max_segment_events, expected_max_tile_bin_events);
+    const FusedLayout F = make_fused_layout(h, o, read_knobs(), B, H, W, expected_max_segment_events, expected_max_tile_bin_events);
     return F.ok ? F.bytes : 0;
 }
 
 extern "C" int v2ce_ldati_count_fused(const float *vox, int B, int H, int W, double fps, double t0,
                                       const v2ce_ldati_options *options, int rng_mode, const float *uniforms, int replay_max_n,
-                                      uint64_t seed, int64_t frame_base, int64_t expected_max_segment_events,
-                                      int64_t expected_max_tile_bin_events, void *tile_ws,
-                                      size_t tile_ws_bytes, void *fused_ws, size_t fused_ws_bytes, int64_t *seg_offsets, int64_t *stats,
+                                      uint64_t seed, int64_t frame_base, int64_t expected_max_segment_events, int64_t expected_max_tile_bin_events,
+                                      void *tile_ws_dev, size_t tile_ws_bytes, void *fused_ws, size_t fused_ws_bytes, int64_t *seg_offsets, int64_t *stats,
                                       v2ce_stream_t stream) {
     clear_error();
-    V2CE_REQUIRE(vox && tile_ws && fused_ws && seg_offsets && stats, V2CE_ERR_BAD_ARG, "v2ce_ldati_count_fused: null pointer");
-    V2CE_REQUIRE(B > 0 && H > 0 && W > 0 && (long long)H * W < (1ll << 30), V2CE_ERR_BAD_ARG,
-                 "v2ce_ldati_count_fused: bad shape B=%d H=%d W=%d", B, H, W);
-    V2CE_REQUIRE(W <= 32767 && H <= 32767, V2CE_ERR_UNSUPPORTED, "v2ce_ldati_count_fused: x/y are int16 (LDATI.py:230-231)");
-    V2CE_REQUIRE(B <= 65535, V2CE_ERR_UNSUPPORTED, "v2ce_ldati_count_fused: B too large for one launch");
-    V2CE_REQUIRE(fps > 0, V2CE_ERR_BAD_ARG, "v2ce_ldati_count_fused: fps must be positive");
-    V2CE_REQUIRE(rng_mode == V2CE_RNG_REPLAY || rng_mode == V2CE_RNG_PHILOX, V2CE_ERR_BAD_ARG,
-                 "v2ce_ldati_count_fused: bad rng_mode %d", rng_mode);
-    V2CE_REQUIRE(rng_mode != V2CE_RNG_REPLAY || replay_max_n == 0 || uniforms != nullptr, V2CE_ERR_BAD_ARG,
-                 "v2ce_ldati_count_fused: REPLAY mode needs the uniform tensor");
+    const char *who = "v2ce_ldati_count_fused";
+    const DrawArgs d{fps, rng_mode, uniforms, replay_max_n, seed, frame_base};
     Opts o;
-    if (int rc = read_options(options, o, "v2ce_ldati_count_fused")) return rc;
+    if (int rc = check_call(who, vox && tile_ws_dev && fused_ws && seg_offsets && stats, B, H, W, true, &d, options, o)) return rc;
+    const Knobs k = read_knobs();
     const HostScalars h = host_scalars(fps, t0, o.bidir, false);
-    const FusedLayout F = make_fused_layout(h, o, B, H, W, expected_max_segment_events, expected_max_tile_bin_events);
-    V2CE_REQUIRE(F.ok, V2CE_ERR_UNSUPPORTED, "v2ce_ldati_count_fused: these arguments have no fused path (v2ce_ldati_fused_ws_bytes = 0)");
-    V2CE_REQUIRE(tile_ws_bytes >= v2ce_ldati_tile_ws_bytes(B, H, W), V2CE_ERR_WORKSPACE,
-                 "v2ce_ldati_count_fused: tile workspace %zu < %zu", tile_ws_bytes, v2ce_ldati_tile_ws_bytes(B, H, W));
-    V2CE_REQUIRE(fused_ws_bytes >= F.bytes, V2CE_ERR_WORKSPACE, "v2ce_ldati_count_fused: workspace %zu < %zu", fused_ws_bytes, F.bytes);
-    V2CE_REQUIRE((reinterpret_cast<uintptr_t>(fused_ws) & 15) == 0, V2CE_ERR_BAD_ARG, "v2ce_ldati_count_fused: workspace must be 16-byte aligned");
+    const FusedLayout F = make_fused_layout(h, o, k, B, H, W, expected_max_segment_events, expected_max_tile_bin_events);
+    const TileWs tw = tile_ws(B, H, W);
+    V2CE_REQUIRE(F.ok, V2CE_ERR_UNSUPPORTED, "%s: these arguments have no fused path (v2ce_ldati_fused_ws_bytes = 0)", who);
+    V2CE_REQUIRE(tile_ws_bytes >= tw.bytes, V2CE_ERR_WORKSPACE, "%s: tile workspace %zu < %zu", who, tile_ws_bytes, tw.bytes);
+    V2CE_REQUIRE(fused_ws_bytes >= F.bytes, V2CE_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, fused_ws_bytes, F.bytes);
+    V2CE_REQUIRE((reinterpret_cast<uintptr_t>(fused_ws) & 15) == 0, V2CE_ERR_BAD_ARG, "%s: workspace must be 16-byte aligned", who);
     hipStream_t s = as_stream(stream);
     const Plan &pl = F.p0;
-    unsigned *tc = static_cast<unsigned *>(tile_ws);
-    unsigned *tile_off = tc + (size_t)B * pl.T * 9;
     if (int rc = probe_lds_order(s)) return rc;
-    unsigned char *fb = static_cast<unsigned char *>(fused_ws);
-    hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<unsigned *>(stats), 16, reinterpret_cast<unsigned *>(fb), 4);
+    if (int rc = zero_words(s, stats, 16, fused_ws, 4)) return rc;
     LdatiParams P{};
-    if (int rc = fill_params(P, h, o, vox, B, H, W, fps, rng_mode, uniforms, replay_max_n, seed, frame_base, s)) return rc;
-    P.shift = pl.shift; P.NB = pl.NB; P.nb1 = pl.nb1; P.T = pl.T; P.Tp = pl.Tp; P.tpp = pl.tpp; P.PB = pl.PB;
+    if (int rc = fill_params(P, h, o, k, vox, B, H, W, d, s)) return rc;
+    set_geometry(P, pl);
+    const PathChoice c = choose_path(o, pl, k, facts_of(P, o, false));
     P.sparse_cap = kSparseCap;
-    P.status = reinterpret_cast<int *>(fb);
-    P.tc_w = tc;
-    P.stats_w = reinterpret_cast<unsigned long long *>(stats);
-    P.tile_abs_w = reinterpret_cast<unsigned *>(fb + F.off_abs);
-    P.temp = reinterpret_cast<unsigned *>(fb + F.off_rec);
-    P.roff = reinterpret_cast<unsigned short *>(fb + F.off_roff);
-    if (F.slot_cap && dense_kernel_serves(P, o)) {
+    P.tc_w = at<unsigned>(tile_ws_dev, tw.tc); P.stats_w = reinterpret_cast<unsigned long long *>(stats);
+    P.status = at<int>(fused_ws, 0); P.tile_abs_w = at<unsigned>(fused_ws, F.off_abs);
+    P.temp = at<unsigned>(fused_ws, F.off_rec); P.roff = at<unsigned short>(fused_ws, F.off_roff);
+    if (F.slot_cap && c.dense_nw) {
         // dense regime: ldati_tile_dense_kernel is the count pass and the tile pass at once (slot mode)
-        P.sparse_cap = 0;
-        P.slot_cap = F.slot_cap;
-        P.capA = pl.capA;
-        launch_dense_kernel(P, pl, B, s);
+        P.sparse_cap = 0; P.slot_cap = F.slot_cap; P.capA = pl.capA;
+        if (int rc = launch_tile_pass(P, pl, c, s)) return rc;
     } else if (F.slot_cap) {
         // (a call the dense kernel does not serve -- more than seven fps values on this device, 64-bit times: the plain count
         // pass, so that the emit phase finds valid counts and takes the two-pass path)
-        hipLaunchKernelGGL(ldati_count_tiles_kernel, dim3(pl.T, B), dim3(kCountThreads), 0, s, vox, H * W, pl.tpp, o.strategy, o.bidir, tc,
-                           reinterpret_cast<unsigned long long *>(stats));
-    } else {
-    auto sparse_kernel = o.bidir ? ldati_tile_sparse_kernel<true, true> : ldati_tile_sparse_kernel<true, false>;
-    V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(sparse_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSparseLds));
-    hipLaunchKernelGGL(sparse_kernel, dim3(pl.T, B), dim3(kSparseThreads), kSparseLds, s, P);
+        hipLaunchKernelGGL(ldati_count_tiles_kernel, dim3(pl.T, B), dim3(kCountThreads), 0, s, vox, H * W, pl.tpp, o.strategy, o.bidir, P.tc_w, P.stats_w);
+    } else if (int rc = launch_sparse_pass<true>(P, pl, c, s)) {
+        return rc;
     }
-    hipLaunchKernelGGL(ldati_tile_scan_kernel, dim3((B + 3) / 4), dim3(256), 0, s, tc, B, pl.T, tile_off, tile_off + (size_t)B * pl.T * 9, pl.Tp,
-                       reinterpret_cast<long long *>(seg_offsets), reinterpret_cast<unsigned long long *>(stats));
-    hipLaunchKernelGGL(ldati_seg_scan_kernel, dim3(1), dim3(256), 0, s, B * 9, reinterpret_cast<long long *>(seg_offsets),
-                       reinterpret_cast<unsigned long long *>(stats));
-    V2CE_HIP_CHECK(hipGetLastError());
-    return V2CE_OK;
+    return launch_count_scans(tw, tile_ws_dev, B, seg_offsets, stats, s);
 }
 
 namespace {
-int emit_impl(const float *vox, int B, int H, int W, double fps, double t0,
-                               const v2ce_ldati_options *options, int rng_mode, const float *uniforms, int replay_max_n,
-                               uint64_t seed, int64_t frame_base, const int64_t *seg_offsets,
-                               const int64_t *frame_ts_add, int64_t *ts, int16_t *x, int16_t *y,
-                               int8_t *p, uint8_t *packed, int64_t total_events,
-                               int64_t max_segment_events, int64_t max_tile_events, const void *tile_ws,
-                               void *workspace, size_t workspace_bytes, v2ce_stream_t stream,
-                               const void *fused_ws, size_t fused_ws_bytes, int64_t fused_tile_max, int64_t fused_seg_hint,
-                               int64_t fused_tile_bin_hint) {
-    clear_error();
-    V2CE_REQUIRE(vox && seg_offsets, V2CE_ERR_BAD_ARG, "v2ce_ldati_emit: null pointer");
-    V2CE_REQUIRE(B > 0 && H > 0 && W > 0 && (long long)H * W < (1ll << 30), V2CE_ERR_BAD_ARG,
-                 "v2ce_ldati_emit: bad shape");
-    V2CE_REQUIRE(W <= 32767 && H <= 32767, V2CE_ERR_UNSUPPORTED, "v2ce_ldati_emit: x/y are int16");
-    V2CE_REQUIRE(fps > 0, V2CE_ERR_BAD_ARG, "v2ce_ldati_emit: fps must be positive");
-    V2CE_REQUIRE(rng_mode == V2CE_RNG_REPLAY || rng_mode == V2CE_RNG_PHILOX, V2CE_ERR_BAD_ARG,
-                 "v2ce_ldati_emit: bad rng_mode %d", rng_mode);
-    Opts o;
-    if (int rc = read_options(options, o, "v2ce_ldati_emit")) return rc;
-    V2CE_REQUIRE(rng_mode != V2CE_RNG_REPLAY || replay_max_n == 0 || uniforms != nullptr,
-                 V2CE_ERR_BAD_ARG, "v2ce_ldati_emit: REPLAY mode needs the uniform tensor");
-    const bool soa = ts && x && y && p;
-    V2CE_REQUIRE(soa != (packed != nullptr) && (soa || !(ts || x || y || p)), V2CE_ERR_BAD_ARG,
-                 "v2ce_ldati_emit: give either the four SoA arrays or the packed buffer");
-    V2CE_REQUIRE(!packed || (reinterpret_cast<uintptr_t>(packed) & 3) == 0, V2CE_ERR_BAD_ARG,
-                 "v2ce_ldati_emit: packed must be 4-byte aligned");
-    const bool random = o.strategy == V2CE_STRATEGY_RANDOM;
-    const HostScalars h = host_scalars(fps, t0, o.bidir, random);
-    V2CE_REQUIRE(h.ok, V2CE_ERR_UNSUPPORTED, "v2ce_ldati_emit: fps=%g t0=%g needs %lld keys per bin (max %d)",
-                 fps, t0, h.NK, kMaxNB << kMaxShift);
-    LdatiParams P{};
-    hipStream_t st = as_stream(stream);
-    if (int rc = fill_params(P, h, o, vox, B, H, W, fps, rng_mode, uniforms, replay_max_n, seed, frame_base, st)) return rc;
-    P.seg_offsets = reinterpret_cast<const long long *>(seg_offsets);
-    P.frame_ts_add = reinterpret_cast<const long long *>(frame_ts_add);
-    P.ts = reinterpret_cast<long long *>(ts); P.x = x; P.y = y;
-    P.p = reinterpret_cast<signed char *>(p);
-    P.packed = packed;
-    if (h.sweep_ok)
-        V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ldati_emit_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds_bytes));
-    if (workspace != nullptr) {
-        V2CE_REQUIRE(tile_ws, V2CE_ERR_BAD_ARG, "v2ce_ldati_emit: the two-level path needs v2ce_ldati_count's tile workspace");
-        V2CE_REQUIRE(total_events >= 0 && max_segment_events >= 0 && max_tile_events >= 0, V2CE_ERR_BAD_ARG,
-                     "v2ce_ldati_emit: bad event counts");
-        const Layout L = make_layout(h, o, B, H, W, total_events, max_segment_events, max_tile_events, packed != nullptr);
-        const Plan &pl = L.plan;
-        V2CE_REQUIRE(L.ok, V2CE_ERR_UNSUPPORTED,
-                     "v2ce_ldati_emit: shape / density outside the two-level path (tiles %d, buckets %d, "
-                     "largest tile-bin %lld events); pass workspace = NULL", pl.T, pl.NB, (long long)max_tile_events);
-        V2CE_REQUIRE(workspace_bytes >= L.bytes, V2CE_ERR_WORKSPACE, "v2ce_ldati_emit: workspace %zu < %zu",
-                     workspace_bytes, L.bytes);
-        unsigned char *wb = static_cast<unsigned char *>(workspace);
-        unsigned *w = static_cast<unsigned *>(workspace);
-        P.shift = pl.shift; P.NB = pl.NB; P.nb1 = pl.nb1; P.T = pl.T; P.Tp = pl.Tp; P.tpp = pl.tpp; P.PB = pl.PB;
-        P.capA = pl.capA; P.cap2 = pl.cap2; P.tbits = pl.tbits;
-        P.tile_off = static_cast<const unsigned *>(tile_ws) + (size_t)B * pl.T * 9;
-        P.tile_src = P.tile_off + (size_t)B * pl.T * 9;
-        P.tc = static_cast<const unsigned *>(tile_ws);
-        // lightly populated tiles (all nine bins <= kSparseCap events) take the one-pass sparse kernel; it needs
-        // the nine bins' keys side by side in 20 bits
-        P.sparse_cap = (!L.generic && 9ll * ((long long)pl.NB << pl.shift) < (1ll << 20) && !getenv("V2CE_LDATI_NO_SPARSE")) ? kSparseCap : 0;
-        P.span = pl.span;
-        P.hist_bins = (4 * (pl.span << pl.shift)) > 4 * kMaxSpanKeys ? (4 * (pl.span << pl.shift)) : 4 * kMaxSpanKeys;
-        if (L.kbb_bytes) {
-            // pooled slope parameters first (LDATI.py:177-190)
-            float2 *kbb = reinterpret_cast<float2 *>(wb + L.bytes - L.kbb_bytes);
-            hipLaunchKernelGGL(ldati_pool_slope_kernel, dim3((P.HW + 255) / 256, 2 * B), dim3(256), 0, st, P, o.pooling,
-                               o.pool_k, kbb);
-            P.kbb = kbb;
-        }
-        auto launch_tile_pass = [&]() -> int {
-            if (!L.generic && dense_kernel_serves(P, o) && dense_tile_lds(pl.capA, pl.NB, 16) <= 160 * 1024) return launch_dense_kernel(P, pl, B, st);
-            auto tile_kernel = o.bidir ? (pl.tile_threads == 512 ? ldati_tile_pass_kernel<512, 4, true> : ldati_tile_pass_kernel<1024, 2, true>)
-                                       : (pl.tile_threads == 512 ? ldati_tile_pass_kernel<512, 4, false> : ldati_tile_pass_kernel<1024, 2, false>);
-            V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(tile_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_tile));
-            hipLaunchKernelGGL(tile_kernel, dim3(pl.T, B), dim3(pl.tile_threads), pl.lds_tile, st, P);
-            return V2CE_OK;
-        };
-        if (L.generic) {
-            // ---- generic path ('random': timestamps spread over a second): tile pass in key mode, one
-            // library radix sort of the 60-bit keys, decode (+ pack)
-            P.status = reinterpret_cast<int *>(wb);
-            hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<unsigned *>(P.status), 4, static_cast<unsigned *>(nullptr), 0);
-            unsigned long long *kA = reinterpret_cast<unsigned long long *>(wb + L.main_bytes);
-            unsigned long long *kB = reinterpret_cast<unsigned long long *>(wb + L.main_bytes + L.keys_bytes / 2);
-            void *tmp = wb + L.main_bytes + L.keys_bytes;
-            P.keys = kA;
-            if (int rc = launch_tile_pass()) return rc;
-            if (total_events > 0) {
-                size_t tb = L.sort_temp_bytes;
-                V2CE_HIP_CHECK(rocprim::radix_sort_keys(tmp, tb, kA, kB, (size_t)total_events, 0, 60, st));
-                long long *ts2 = P.ts;
-                short *x2 = P.x, *y2 = P.y;
-                signed char *p2 = P.p;
-                if (packed) {
-                    unsigned char *sb = wb + L.main_bytes + L.keys_bytes + L.sort_temp_bytes;
-                    ts2 = reinterpret_cast<long long *>(sb);
-                    x2 = reinterpret_cast<short *>(sb + 8 * (size_t)total_events);
-                    y2 = x2 + total_events;
-                    p2 = reinterpret_cast<signed char *>(y2 + total_events);
-                }
-                const long long blocks = (total_events + 255) / 256;
-                hipLaunchKernelGGL(ldati_keys_decode_kernel, dim3((unsigned)blocks), dim3(256), 0, st, P, kB,
-                                   (long long)total_events, ts2, x2, y2, p2);
-                if (packed)
-                    hipLaunchKernelGGL(events_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ts2, x2, y2, p2,
-                                       (long long)total_events, packed);
-            }
-            V2CE_HIP_CHECK(hipGetLastError());
-            return V2CE_OK;
-        }
-        // ---- two-level path; segments with an oversized bucket fall through to the sweep kernel
-        P.bofs = w;
-        P.groups = P.bofs + pl.n_bkt;
-        P.big_list = P.groups + (size_t)B * 9 * pl.NB;
-        P.ngroups = P.big_list + (size_t)B * 9 * pl.NB;
-        P.seg_flag = reinterpret_cast<int *>(P.ngroups + (size_t)B * 9);
-        P.status = P.seg_flag + (size_t)B * 9;
-        P.nbig = reinterpret_cast<unsigned *>(P.status + 1);
-        P.temp = reinterpret_cast<unsigned *>(P.status + 4);
-        P.roff = reinterpret_cast<unsigned short *>(P.temp + (size_t)total_events);
-        P.gruns = reinterpret_cast<unsigned *>(P.roff + ((pl.n_tab + 1) & ~(size_t)1));
-        hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<unsigned *>(P.status), 4, static_cast<unsigned *>(nullptr), 0);
-        // the fused count already ran the sparse tile pass: usable when its assumed geometry is the plan's and every tile fitted
-        bool fused = false;
-        if (fused_ws && !P.kbb && (fused_tile_bin_hint > 0 || P.sparse_cap)) {
-            const FusedLayout F = make_fused_layout(h, o, B, H, W, fused_seg_hint, fused_tile_bin_hint);
-            // sparse form: every tile fitted its slot; dense form: the dense kernel ran (count_fused's own test) and every (tile, bin) run fitted
-            fused = F.ok && fused_ws_bytes >= F.bytes && F.p0.shift == pl.shift && F.p0.NB == pl.NB && F.p0.T == pl.T &&
-                    (F.slot_cap ? dense_kernel_serves(P, o) && max_tile_events <= F.slot_cap : fused_tile_max <= kSparseCap);
-            if (getenv("V2CE_LDATI_DEBUG"))
-                fprintf(stderr, "v2ce_ldati_emit_fused: fused=%d ok=%d bytes %zu/%zu tile_max=%lld shift %d/%d NB %d/%d T %d/%d max_segment %lld sort threads %d cap2 %d\n", (int)fused, (int)F.ok,
-                        fused_ws_bytes, F.bytes, (long long)fused_tile_max, F.p0.shift, pl.shift, F.p0.NB, pl.NB, F.p0.T, pl.T, (long long)max_segment_events, pl.sort_threads, pl.cap2);
-            if (getenv("V2CE_LDATI_DEBUG") && F.slot_cap) fprintf(stderr, "   dense slots of %d records, largest (tile, bin) %lld\n", F.slot_cap, (long long)max_tile_events);
-            if (fused) {
-                const unsigned char *fb = static_cast<const unsigned char *>(fused_ws);
-                P.fused_status = reinterpret_cast<const int *>(fb);
-                P.tile_abs = reinterpret_cast<const unsigned *>(fb + F.off_abs);
-                P.tile_src = P.tile_abs;
-                P.temp = const_cast<unsigned *>(reinterpret_cast<const unsigned *>(fb + F.off_rec));
-                P.roff = const_cast<unsigned short *>(reinterpret_cast<const unsigned short *>(fb + F.off_roff));
-            }
-        }
-        // (Tried in round 3 and removed: walking the frames in groups so that the HBM-bound bucket sort of group g runs on a
-        // low-priority side stream under the VALU-bound tile pass of group g + 1.  24 stress frame-pairs: 1 group 1.74 ms,
-        // 2 groups 1.86, 4 groups 1.83, 8 groups 2.21 -- the tile pass needs whole CUs (1024 threads, ~100 KB of LDS), the sort
-        // workgroups that slip in between delay its rounds, and each group adds a partial last round.)
-        if (P.sparse_cap && !fused) {
-            auto sparse_kernel = o.bidir ? ldati_tile_sparse_kernel<false, true> : ldati_tile_sparse_kernel<false, false>;
-            V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(sparse_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSparseLds));
-            hipLaunchKernelGGL(sparse_kernel, dim3(pl.T, B), dim3(kSparseThreads), kSparseLds, st, P);
-        }
-        if (!fused)
-            if (int rc = launch_tile_pass()) return rc;
-        hipLaunchKernelGGL(ldati_bucket_scan_kernel, dim3(B * 9), dim3(512), 0, st, P);
-        {
-            const bool k24 = pl.cap2 > pl.sort_threads * 8;
-            const int sth = pl.sort_threads;
-            auto sort_kernel = packed ? (k24 ? (sth == 64 ? ldati_bucket_sort_kernel<true, 24, 64> : sth == 128 ? ldati_bucket_sort_kernel<true, 24, 128> : ldati_bucket_sort_kernel<true, 24, 256>)
-                                             : ldati_bucket_sort_kernel<true, 8, 256>)
-                                      : (k24 ? (sth == 64 ? ldati_bucket_sort_kernel<false, 24, 64> : sth == 128 ? ldati_bucket_sort_kernel<false, 24, 128> : ldati_bucket_sort_kernel<false, 24, 256>)
-                                             : ldati_bucket_sort_kernel<false, 8, 256>);
-            V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(sort_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_sort));
-            hipLaunchKernelGGL(sort_kernel, dim3(pl.NB, B * 9), dim3(pl.sort_threads), pl.lds_sort, st, P);
-        }
-        if (packed) hipLaunchKernelGGL(ldati_big_bucket_kernel<true>, dim3(256), dim3(256), 0, st, P);
-        else hipLaunchKernelGGL(ldati_big_bucket_kernel<false>, dim3(256), dim3(256), 0, st, P);
-        V2CE_HIP_CHECK(hipGetLastError());
-        return V2CE_OK;
-    } else {
-        V2CE_REQUIRE(h.sweep_ok && o.pooling == V2CE_POOL_NONE, V2CE_ERR_UNSUPPORTED,
-                     "v2ce_ldati_emit: the sweep kernel (workspace = NULL) covers forward relocation without pooling at "
-                     "key ranges <= 9600 (fps=%g t0=%g needs %lld keys per bin): pass a workspace", fps, t0, h.NK);
-    }
-    // segment-sweep kernel (workspace = NULL): every segment
-    hipLaunchKernelGGL(ldati_emit_kernel, dim3(B * 9), dim3(256), h.lds_bytes, st, P);
+// the arguments of v2ce_ldati_emit / v2ce_ldati_emit_fused, in the order of their parameter lists
+struct EmitArgs {
+    const float *vox; int B, H, W; double fps, t0; const v2ce_ldati_options *options;
+    DrawArgs draw;
+    const int64_t *seg_offsets, *frame_ts_add; int64_t *ts; int16_t *x, *y; int8_t *p; uint8_t *packed;
+    int64_t total_events, max_segment_events, max_tile_events; const void *tile_ws; void *workspace; size_t workspace_bytes;
+    const void *fused_ws; size_t fused_ws_bytes; int64_t fused_tile_max, fused_seg_hint, fused_tile_bin_hint;   // emit_fused only
+    v2ce_stream_t stream;
+};
+
+// segment-sweep kernel (workspace = NULL): one workgroup per segment, every segment; what the two-level path is tested against
+int emit_sweep(const EmitArgs &a, const HostScalars &h, const Opts &o, const LdatiParams &P, hipStream_t st) {
+    V2CE_REQUIRE(h.sweep_ok && o.pooling == V2CE_POOL_NONE, V2CE_ERR_UNSUPPORTED, "v2ce_ldati_emit: the sweep kernel (workspace = NULL) covers forward relocation "
+                 "without pooling at key ranges <= 9600 (fps=%g t0=%g needs %lld keys per bin): pass a workspace", a.fps, a.t0, h.NK);
+    V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ldati_emit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds_bytes));
+    hipLaunchKernelGGL(ldati_emit_kernel, dim3(a.B * 9), dim3(256), h.lds_bytes, st, P);
     V2CE_HIP_CHECK(hipGetLastError());
     return V2CE_OK;
 }
 
-}  // namespace
-
-extern "C" int v2ce_ldati_emit(const float *vox, int B, int H, int W, double fps, double t0,
-                               const v2ce_ldati_options *options, int rng_mode, const float *uniforms, int replay_max_n,
-                               uint64_t seed, int64_t frame_base, const int64_t *seg_offsets,
-                               const int64_t *frame_ts_add, int64_t *ts, int16_t *x, int16_t *y,
-                               int8_t *p, uint8_t *packed, int64_t total_events,
-                               int64_t max_segment_events, int64_t max_tile_events, const void *tile_ws,
-                               void *workspace, size_t workspace_bytes, v2ce_stream_t stream) {
-    return emit_impl(vox, B, H, W, fps, t0, options, rng_mode, uniforms, replay_max_n, seed, frame_base, seg_offsets, frame_ts_add, ts, x,
-                     y, p, packed, total_events, max_segment_events, max_tile_events, tile_ws, workspace, workspace_bytes, stream,
-                     nullptr, 0, 0, 0, 0);
+// generic path ('random': timestamps spread over a second): tile pass in key mode, one library radix sort of the 60-bit keys, decode (+ pack)
+int emit_generic(const EmitArgs &a, LdatiParams &P, const Plan &pl, const PathChoice &c, const TwoLevelWs &w, hipStream_t st) {
+    const size_t n = (size_t)a.total_events;
+    unsigned long long *kA = at<unsigned long long>(a.workspace, w.keys), *kB = at<unsigned long long>(a.workspace, w.keys_alt);
+    P.keys = kA;
+    if (int rc = launch_tile_pass(P, pl, c, st)) return rc;
+    if (n > 0) {
+        size_t tb = w.soa - w.sort_temp;
+        V2CE_HIP_CHECK(rocprim::radix_sort_keys(at<unsigned char>(a.workspace, w.sort_temp), tb, kA, kB, n, 0, 60, st));
+        // packed output: decode into the SoA arrays of the workspace, then pack
+        long long *ts2 = a.packed ? at<long long>(a.workspace, w.soa) : P.ts;
+        short *x2 = a.packed ? at<short>(a.workspace, w.soa + 8 * n) : P.x, *y2 = a.packed ? x2 + n : P.y;
+        signed char *p2 = a.packed ? reinterpret_cast<signed char *>(y2 + n) : P.p;
+        const unsigned blocks = (unsigned)((a.total_events + 255) / 256);
+        hipLaunchKernelGGL(ldati_keys_decode_kernel, dim3(blocks), dim3(256), 0, st, P, kB, (long long)n, ts2, x2, y2, p2);
+        if (a.packed) hipLaunchKernelGGL(events_pack_kernel, dim3(blocks), dim3(256), 0, st, ts2, x2, y2, p2, (long long)n, a.packed);
+    }
+    V2CE_HIP_CHECK(hipGetLastError());
+    return V2CE_OK;
 }
 
-extern "C" int v2ce_ldati_emit_fused(const float *vox, int B, int H, int W, double fps, double t0,
-                                     const v2ce_ldati_options *options, int rng_mode, const float *uniforms, int replay_max_n,
-                                     uint64_t seed, int64_t frame_base, const int64_t *seg_offsets,
-                                     const int64_t *frame_ts_add, int64_t *ts, int16_t *x, int16_t *y,
-                                     int8_t *p, uint8_t *packed, int64_t total_events,
-                                     int64_t max_segment_events, int64_t max_tile_events, const void *tile_ws,
-                                     void *workspace, size_t workspace_bytes, const void *fused_ws, size_t fused_ws_bytes,
-                                     int64_t largest_tile_events, int64_t expected_max_segment_events,
+// two-level path: [sparse tile kernel, tile pass -- unless the fused count left their records] -> bucket scan -> bucket sort -> big buckets
+int emit_two_level(const EmitArgs &a, const HostScalars &h, const Opts &o, const Knobs &k, LdatiParams &P, const Plan &pl, const PathChoice &c, const TwoLevelWs &w, hipStream_t st) {
+    P.bofs = at<unsigned>(a.workspace, w.bofs); P.groups = at<unsigned>(a.workspace, w.groups);
+    P.big_list = at<unsigned>(a.workspace, w.big_list); P.ngroups = at<unsigned>(a.workspace, w.ngroups);
+    P.seg_flag = at<int>(a.workspace, w.seg_flag); P.nbig = at<unsigned>(a.workspace, w.status + 4);
+    P.temp = at<unsigned>(a.workspace, w.temp); P.roff = at<unsigned short>(a.workspace, w.roff);
+    P.gruns = at<unsigned>(a.workspace, w.gruns);
+    // the fused count already ran the tile pass: usable when the call has a fused path at all (F.ok), its assumed geometry is the plan's and every tile fitted
+    bool fused = false;
+    if (a.fused_ws) {
+        const FusedLayout F = make_fused_layout(h, o, k, a.B, a.H, a.W, a.fused_seg_hint, a.fused_tile_bin_hint);
+        // sparse form: every tile fitted its slot; dense form: the dense kernel ran (count_fused's own test) and every (tile, bin) run fitted
+        fused = F.ok && a.fused_ws_bytes >= F.bytes && F.p0.shift == pl.shift && F.p0.NB == pl.NB && F.p0.T == pl.T &&
+                (F.slot_cap ? choose_path(o, F.p0, k, facts_of(P, o, false)).dense_nw && a.max_tile_events <= F.slot_cap : a.fused_tile_max <= kSparseCap);
+        if (k.debug) {
+            fprintf(stderr, "v2ce_ldati_emit_fused: fused=%d ok=%d bytes %zu/%zu tile_max=%lld shift %d/%d NB %d/%d T %d/%d max_segment %lld sort threads %d cap2 %d\n", (int)fused,
+                    (int)F.ok, a.fused_ws_bytes, F.bytes, (long long)a.fused_tile_max, F.p0.shift, pl.shift, F.p0.NB, pl.NB, F.p0.T, pl.T, (long long)a.max_segment_events, pl.sort_threads, pl.cap2);
+            if (F.slot_cap) fprintf(stderr, "   dense slots of %d records, largest (tile, bin) %lld\n", F.slot_cap, (long long)a.max_tile_events);
+        }
+        if (fused) {
+            P.fused_status = at<const int>(a.fused_ws, 0);
+            P.tile_src = P.tile_abs = at<const unsigned>(a.fused_ws, F.off_abs);
+            P.temp = at<unsigned>(a.fused_ws, F.off_rec); P.roff = at<unsigned short>(a.fused_ws, F.off_roff);
+        }
+    }
+    // (Tried in round 3 and removed: walking the frames in groups so that the HBM-bound bucket sort of group g runs on a
+    // low-priority side stream under the VALU-bound tile pass of group g + 1.  24 stress frame-pairs: 1 group 1.74 ms,
+    // 2 groups 1.86, 4 groups 1.83, 8 groups 2.21 -- the tile pass needs whole CUs (1024 threads, ~100 KB of LDS), the sort
+    // workgroups that slip in between delay its rounds, and each group adds a partial last round.)
+    if (!fused) {
+        if (c.sparse_cap)
+            if (int rc = launch_sparse_pass<false>(P, pl, c, st)) return rc;
+        if (int rc = launch_tile_pass(P, pl, c, st)) return rc;
+    }
+    hipLaunchKernelGGL(ldati_bucket_scan_kernel, dim3(a.B * 9), dim3(512), 0, st, P);
+    auto sort_kernel = c.sort_packed ? sort_kernel_of<true>(c) : sort_kernel_of<false>(c);
+    V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_sort));
+    hipLaunchKernelGGL(sort_kernel, dim3(pl.NB, a.B * 9), dim3(c.sort_threads), pl.lds_sort, st, P);
+    hipLaunchKernelGGL(c.sort_packed ? ldati_big_bucket_kernel<true> : ldati_big_bucket_kernel<false>, dim3(256), dim3(256), 0, st, P);
+    V2CE_HIP_CHECK(hipGetLastError());
+    return V2CE_OK;
+}
+
+int emit(const EmitArgs &a) {
+    clear_error();
+    const char *who = "v2ce_ldati_emit";
+    Opts o;
+    if (int rc = check_call(who, a.vox && a.seg_offsets, a.B, a.H, a.W, false, &a.draw, a.options, o)) return rc;
+    const bool soa = a.ts && a.x && a.y && a.p;
+    V2CE_REQUIRE(soa != (a.packed != nullptr) && (soa || !(a.ts || a.x || a.y || a.p)), V2CE_ERR_BAD_ARG, "%s: give either the four SoA arrays or the packed buffer", who);
+    V2CE_REQUIRE(!a.packed || (reinterpret_cast<uintptr_t>(a.packed) & 3) == 0, V2CE_ERR_BAD_ARG, "%s: packed must be 4-byte aligned", who);
+    const HostScalars h = host_scalars(a.fps, a.t0, o.bidir, o.strategy == V2CE_STRATEGY_RANDOM);
+    V2CE_REQUIRE(h.ok, V2CE_ERR_UNSUPPORTED, "%s: fps=%g t0=%g needs %lld keys per bin (max %d)", who, a.fps, a.t0, h.NK, kMaxNB << kMaxShift);
+    const Knobs k = read_knobs();
+    LdatiParams P{};
+    hipStream_t st = as_stream(a.stream);
+    if (int rc = fill_params(P, h, o, k, a.vox, a.B, a.H, a.W, a.draw, st)) return rc;
+    P.seg_offsets = reinterpret_cast<const long long *>(a.seg_offsets); P.frame_ts_add = reinterpret_cast<const long long *>(a.frame_ts_add);
+    P.ts = reinterpret_cast<long long *>(a.ts); P.x = a.x; P.y = a.y; P.p = reinterpret_cast<signed char *>(a.p);
+    P.packed = a.packed;
+    if (!a.workspace) return emit_sweep(a, h, o, P, st);
+    V2CE_REQUIRE(a.tile_ws, V2CE_ERR_BAD_ARG, "%s: the two-level path needs v2ce_ldati_count's tile workspace", who);
+    V2CE_REQUIRE(a.total_events >= 0 && a.max_segment_events >= 0 && a.max_tile_events >= 0, V2CE_ERR_BAD_ARG, "%s: bad event counts", who);
+    const Plan pl = make_plan(h, k, a.B, a.H, a.W, a.total_events, a.max_segment_events, a.max_tile_events);
+    const TwoLevelWs w = workspace_of(pl, o, a.B, a.H, a.W, a.total_events, a.packed != nullptr);
+    V2CE_REQUIRE(w.ok, V2CE_ERR_UNSUPPORTED, "%s: shape / density outside the two-level path (tiles %d, buckets %d, largest tile-bin %lld events); pass workspace = NULL",
+                 who, pl.T, pl.NB, (long long)a.max_tile_events);
+    V2CE_REQUIRE(a.workspace_bytes >= w.bytes, V2CE_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, a.workspace_bytes, w.bytes);
+    const TileWs tw = tile_ws(a.B, a.H, a.W);
+    const PathChoice c = choose_path(o, pl, k, facts_of(P, o, a.packed != nullptr));
+    set_geometry(P, pl);
+    P.capA = pl.capA; P.cap2 = pl.cap2; P.tbits = pl.tbits; P.span = pl.span;
+    P.tc = at<const unsigned>(a.tile_ws, tw.tc); P.tile_off = at<const unsigned>(a.tile_ws, tw.tile_off); P.tile_src = at<const unsigned>(a.tile_ws, tw.tile_src);
+    P.sparse_cap = c.sparse_cap; P.hist_bins = c.hist_bins;
+    if (w.bytes > w.kbb) {
+        // pooled slope parameters first (LDATI.py:177-190)
+        float2 *kbb = at<float2>(a.workspace, w.kbb);
+        hipLaunchKernelGGL(ldati_pool_slope_kernel, dim3((P.HW + 255) / 256, 2 * a.B), dim3(256), 0, st, P, o.pooling, o.pool_k, kbb);
+        P.kbb = kbb;
+    }
+    P.status = at<int>(a.workspace, w.status);
+    if (int rc = zero_words(st, P.status, 4)) return rc;
+    return c.generic ? emit_generic(a, P, pl, c, w, st) : emit_two_level(a, h, o, k, P, pl, c, w, st);
+}
+}  // namespace
+
+extern "C" int v2ce_ldati_emit(const float *vox, int B, int H, int W, double fps, double t0, const v2ce_ldati_options *options, int rng_mode,
+                               const float *uniforms, int replay_max_n, uint64_t seed, int64_t frame_base, const int64_t *seg_offsets,
+                               const int64_t *frame_ts_add, int64_t *ts, int16_t *x, int16_t *y, int8_t *p, uint8_t *packed, int64_t total_events,
+                               int64_t max_segment_events, int64_t max_tile_events, const void *tile_ws, void *workspace, size_t workspace_bytes,
+                               v2ce_stream_t stream) {
+    return emit(EmitArgs{vox, B, H, W, fps, t0, options, DrawArgs{fps, rng_mode, uniforms, replay_max_n, seed, frame_base}, seg_offsets, frame_ts_add, ts, x, y, p,
+                         packed, total_events, max_segment_events, max_tile_events, tile_ws, workspace, workspace_bytes, nullptr, 0, 0, 0, 0, stream});
+}
+
+extern "C" int v2ce_ldati_emit_fused(const float *vox, int B, int H, int W, double fps, double t0, const v2ce_ldati_options *options, int rng_mode,
+                                     const float *uniforms, int replay_max_n, uint64_t seed, int64_t frame_base, const int64_t *seg_offsets,
+                                     const int64_t *frame_ts_add, int64_t *ts, int16_t *x, int16_t *y, int8_t *p, uint8_t *packed, int64_t total_events,
+                                     int64_t max_segment_events, int64_t max_tile_events, const void *tile_ws, void *workspace, size_t workspace_bytes,
+                                     const void *fused_ws, size_t fused_ws_bytes, int64_t largest_tile_events, int64_t expected_max_segment_events,
                                      int64_t expected_max_tile_bin_events, v2ce_stream_t stream) {
-    return emit_impl(vox, B, H, W, fps, t0, options, rng_mode, uniforms, replay_max_n, seed, frame_base, seg_offsets, frame_ts_add, ts, x,
-                     y, p, packed, total_events, max_segment_events, max_tile_events, tile_ws, workspace, workspace_bytes, stream,
-                     fused_ws, fused_ws_bytes, largest_tile_events, expected_max_segment_events, expected_max_tile_bin_events);
+    return emit(EmitArgs{vox, B, H, W, fps, t0, options, DrawArgs{fps, rng_mode, uniforms, replay_max_n, seed, frame_base}, seg_offsets, frame_ts_add, ts, x, y, p,
+                         packed, total_events, max_segment_events, max_tile_events, tile_ws, workspace, workspace_bytes, fused_ws, fused_ws_bytes,
+                         largest_tile_events, expected_max_segment_events, expected_max_tile_bin_events, stream});
 }
 
 extern "C" int v2ce_ldati_plan_info(int B, int H, int W, double fps, double t0, const v2ce_ldati_options *options,
@@ -3586,30 +2749,24 @@ extern "C" int v2ce_ldati_plan_info(int B, int H, int W, double fps, double t0, 
     Opts o;
     if (int rc = read_options(options, o, "v2ce_ldati_plan_info")) return rc;
     const HostScalars h = host_scalars(fps, t0, o.bidir, o.strategy == V2CE_STRATEGY_RANDOM);
-    const Plan pl = make_plan(h, B, H, W, total_events, max_segment_events, max_tile_events);
-    const int64_t v[10] = {pl.ok, pl.shift, pl.NB, pl.T, pl.capA, pl.cap2, (int64_t)pl.n_tab, (int64_t)pl.n_bkt,
-                           (int64_t)pl.lds_tile, (int64_t)pl.lds_sort};   // workspace layout: see v2ce_hip.h
+    const Plan pl = make_plan(h, read_knobs(), B, H, W, total_events, max_segment_events, max_tile_events);
+    // (workspace layout: TwoLevelWs, ldati_plan.h)
+    const int64_t v[10] = {pl.ok, pl.shift, pl.NB, pl.T, pl.capA, pl.cap2, (int64_t)pl.n_tab, (int64_t)pl.n_bkt, (int64_t)pl.lds_tile, (int64_t)pl.lds_sort};
     for (int i = 0; i < 10; ++i) info[i] = v[i];
     return V2CE_OK;
 }
 
-extern "C" int v2ce_ldati_status(const void *workspace, int B, int H, int W, double fps, double t0,
-                                 const v2ce_ldati_options *options, int64_t total_events, int64_t max_segment_events,
-                                 int64_t max_tile_events, const int32_t **status_dev) {
+extern "C" int v2ce_ldati_status(const void *workspace, int B, int H, int W, double fps, double t0, const v2ce_ldati_options *options,
+                                 int64_t total_events, int64_t max_segment_events, int64_t max_tile_events, const int32_t **status_dev) {
     clear_error();
     V2CE_REQUIRE(workspace && status_dev, V2CE_ERR_BAD_ARG, "v2ce_ldati_status: null pointer");
     Opts o;
     if (int rc = read_options(options, o, "v2ce_ldati_status")) return rc;
-    const bool random = o.strategy == V2CE_STRATEGY_RANDOM;
-    const HostScalars h = host_scalars(fps, t0, o.bidir, random);
-    const Plan pl = make_plan(h, B, H, W, total_events, max_segment_events, max_tile_events);
-    const unsigned *w = static_cast<const unsigned *>(workspace);
-    if (random) {
-        *status_dev = reinterpret_cast<const int32_t *>(w);
-        return V2CE_OK;
-    }
-    V2CE_REQUIRE(pl.ok, V2CE_ERR_UNSUPPORTED, "v2ce_ldati_status: no two-level plan for these arguments");
-    *status_dev = reinterpret_cast<const int32_t *>(w + pl.n_bkt + 2 * (size_t)B * 9 * pl.NB + 2 * (size_t)B * 9);
+    const HostScalars h = host_scalars(fps, t0, o.bidir, o.strategy == V2CE_STRATEGY_RANDOM);
+    const Plan pl = make_plan(h, read_knobs(), B, H, W, total_events, max_segment_events, max_tile_events);
+    const TwoLevelWs w = two_level_ws(pl, o, B, H, W, total_events, false, 0);   // (the status word sits in front of everything these two size)
+    V2CE_REQUIRE(w.generic || pl.ok, V2CE_ERR_UNSUPPORTED, "v2ce_ldati_status: no two-level plan for these arguments");
+    *status_dev = at<const int32_t>(workspace, w.status);
     return V2CE_OK;
 }
 
@@ -3618,8 +2775,7 @@ extern "C" int v2ce_ldati_rank_mode(int32_t *mode) {
     V2CE_REQUIRE(mode, V2CE_ERR_BAD_ARG, "v2ce_ldati_rank_mode: null pointer");
     int ok = 0;
     V2CE_HIP_CHECK(hipMemcpyFromSymbol(&ok, HIP_SYMBOL(g_lds_order_ok), sizeof(int)));
-    const char *e = getenv("V2CE_LDATI_NO_ATOMIC_ORDER");
-    *mode = (ok && !(e && e[0] == '1')) ? 1 : 0;
+    *mode = (ok && !read_knobs().ballot_ranks) ? 1 : 0;
     return V2CE_OK;
 }
 
