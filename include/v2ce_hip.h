@@ -605,6 +605,53 @@ int v2ce_event_grids_batch(const int64_t *ts, const int16_t *x, const int16_t *y
                            double *count, double *mean, double *std, int32_t *status, void *workspace,
                            size_t workspace_bytes, v2ce_stream_t stream);
 
+/* Physical-attention maps (csrc/physatt.hip): train/scripts/utils/physical_att.py on the device, P frame pairs and the
+ * events between their frames in one call.  frames_u8: uint8, either a clip [P+1][H][W] (pair i = frames i and i + 1,
+ * pair_stride = 1) or stacked pairs [P][2][H][W] (pair_stride = 2); events as SoA columns x, y int16 (time and polarity
+ * play no part, physical_att.py:41-44), pair i owns events [offsets[i], offsets[i+1]) (int64 [P+1], device).
+ * Hp = ceil(H / pool_size), Wp = ceil(W / pool_size); out_map f32 [P][Hp][Wp]; out_mask uint8 [P][Hp][Wp] (0 / 1; may
+ * be NULL unless K > 0).  lut: DEVICE float32 [256], the reference's lin_log (v2e_utils.py:5-43) of v + 1e-6 for the 256
+ * pixel values, built by the host; gauss_w: HOST float64 [5], exp(-k^2 / 2) / sum_{-4..4} for k = 0 .. 4 (read during
+ * the call, unused in the RATIO mode).  Arithmetic, all float32 with separately rounded operations unless stated:
+ *   ev    = (events in the patch) / pool_size^2  (the zero-padded block mean of the count frame, exact below 2^24)
+ *   delta = zero-padded block mean of |lut[b] - lut[a]| (RATIO: of that / threshold) in the order of np.mean over
+ *           skimage's block view: every block row with NumPy's pairwise inner loop (n < 8: left to right; else eight
+ *           accumulators, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the remainder left to right), the row sums added in row
+ *           order from zero, then / pool_size^2
+ *   V2CE_PHYSATT_PLAIN / _ADVANCED (physical_attention_generation :107-146 / _advanced :150-193): ev < 0.05 -> 0;
+ *           ev / (delta + 1e-3); clip [0, 2 * ceiling]; scipy.ndimage.gaussian_filter(sigma = 1): radius 4, mode reflect,
+ *           axis 0 then axis 1, each pass x0 * w0 + sum_{j = 4..1} (x[-j] + x[+j]) * wj in float64, stored as float32;
+ *           clip [0, ceiling]; all zeros if max == min, else map / ceiling (PLAIN) or (map - min) / (max - min) (ADVANCED)
+ *   V2CE_PHYSATT_RATIO (the ratio_map of physical_mask_generation :64-84): ev / (delta + 1e-6) - 1; with K > 0 also
+ *           out_mask = ratio >= (K-th largest ratio), more than K cells on a tie; 1 <= K <= Hp * Wp
+ * Only integer atomics: the bytes are the same from run to run and do not depend on the other pairs of the call.
+ * status [P] int32 (device), one word per pair; a pair with a bit set gets a zero map (and mask), the others are
+ * unaffected:
+ *   V2CE_PHYSATT_BAD_XY          an x / y outside W x H, negative ones included
+ *   V2CE_PHYSATT_BAD_OFFSETS     offsets[i] > offsets[i+1], or outside [0, n]: the table lives on the device and the
+ *                                entry does not synchronise, so a descending table is reported here and not by the
+ *                                return code; no table makes a kernel read or write out of bounds
+ *   V2CE_PHYSATT_COUNT_OVERFLOW  a patch holds 2^24 events or more, where the reference's float32 sum is not exact
+ * pool_size outside [2, 16], Hp * Wp above 6144 (the finishing kernel's LDS; 260 x 346 fits from pool_size 4 on), H or W
+ * above 32767 or n >= 2^31 is V2CE_ERR_UNSUPPORTED, and v2ce_physatt_workspace_bytes returns 0.  A pair without events
+ * is valid.
+ *
+ * v2ce_log_residual_batch: gen_log_frame_residual_batch (:232-247): out f32 [N-1][1][H][W] = lut[f[i+1]] - lut[f[i]],
+ * lut the DEVICE float32 [256] table of lin_log(v) (no 1e-6 here).  N >= 2. */
+#define V2CE_PHYSATT_PLAIN 0
+#define V2CE_PHYSATT_ADVANCED 1
+#define V2CE_PHYSATT_RATIO 2
+#define V2CE_PHYSATT_BAD_XY 1
+#define V2CE_PHYSATT_BAD_OFFSETS 2
+#define V2CE_PHYSATT_COUNT_OVERFLOW 4
+size_t v2ce_physatt_workspace_bytes(int P, int H, int W, int pool_size, int64_t n_events);
+int v2ce_physatt_batch(const uint8_t *frames_u8, int pair_stride, int P, int H, int W, const int16_t *x, const int16_t *y,
+                       const int64_t *offsets, int64_t n, int pool_size, int mode, float ceiling, float threshold, int K,
+                       const float *lut, const double *gauss_w, float *out_map, uint8_t *out_mask, int32_t *status,
+                       void *workspace, size_t workspace_bytes, v2ce_stream_t stream);
+int v2ce_log_residual_batch(const uint8_t *frames_u8, int N, int H, int W, const float *lut, float *out,
+                            v2ce_stream_t stream);
+
 /* Event-frame video (csrc/event_frames.hip): the array work of write_event_frame_video (v2ce.py:253-269,275-276) on
  * the device.  mode: V2CE_EVENT_FRAMES_POLARITY = keep_polarity=True (channels S0, S1 and a zero plane, float64
  * arithmetic, v2ce.py:255-257), V2CE_EVENT_FRAMES_GREY = keep_polarity=False (S2 three times, float32, v2ce.py:259-260).

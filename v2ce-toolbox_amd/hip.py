@@ -38,6 +38,7 @@ EXPORTS = [
     "v2ce_voxmetrics_workspace_bytes", "v2ce_voxmetrics", "v2ce_voxelize_batch_workspace_bytes", "v2ce_voxelize_batch",
     "v2ce_event_frames_hist_bytes", "v2ce_event_frames_sums", "v2ce_event_frames_refine", "v2ce_event_frames_render",
     "v2ce_event_grids_workspace_bytes", "v2ce_event_grids_batch",
+    "v2ce_physatt_workspace_bytes", "v2ce_physatt_batch", "v2ce_log_residual_batch",
 ]
 
 
@@ -95,6 +96,9 @@ VOXELIZE_EMPTY, VOXELIZE_SINGLE_TIMESTAMP, VOXELIZE_BAD_XY, VOXELIZE_BAD_RANGE =
 EVENT_GRIDS_SIGNED, EVENT_GRIDS_SPLIT, EVENT_GRIDS_STAT = 1, 2, 4
 (EVENT_GRIDS_EMPTY, EVENT_GRIDS_BAD_XY, EVENT_GRIDS_BAD_TIME, EVENT_GRIDS_STAT_TOP_EDGE,
  EVENT_GRIDS_STAT_OVERFLOW) = 1, 2, 4, 8, 16
+
+PHYSATT_PLAIN, PHYSATT_ADVANCED, PHYSATT_RATIO = 0, 1, 2
+PHYSATT_BAD_XY, PHYSATT_BAD_OFFSETS, PHYSATT_COUNT_OVERFLOW = 1, 2, 4
 
 EVENT_FRAMES_POLARITY, EVENT_FRAMES_GREY = 0, 1
 EVENT_FRAMES_LEVEL0_BINS, EVENT_FRAMES_REFINE_BINS = 2048, 1024
@@ -243,6 +247,13 @@ def lib() -> ctypes.CDLL:
     L.v2ce_event_grids_workspace_bytes.restype = sz
     L.v2ce_event_grids_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.v2ce_event_grids_batch.restype = ctypes.c_int
+    L.v2ce_physatt_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
+    L.v2ce_physatt_workspace_bytes.restype = sz
+    L.v2ce_physatt_batch.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, i64, i32, i32, ctypes.c_float, ctypes.c_float, i32,
+                                     vp, ctypes.POINTER(ctypes.c_double), vp, vp, vp, vp, sz, vp]
+    L.v2ce_physatt_batch.restype = ctypes.c_int
+    L.v2ce_log_residual_batch.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    L.v2ce_log_residual_batch.restype = ctypes.c_int
     L.v2ce_event_frames_hist_bytes.argtypes = [i32]
     L.v2ce_event_frames_hist_bytes.restype = sz
     L.v2ce_event_frames_sums.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
