@@ -345,9 +345,15 @@ int v2ce_conv3d_fwd_tail(const v2ce_conv3d_desc *desc, const float *x0, const fl
  * 1 KB contiguous stores of the channels-last-16 layout.  desc: C0 = 2, C1 = 0, Cout = 32, ksize 3, stride 1, layout C16 (the
  * layout of y; x is the planar network input [B][T][2][H][W0_pitch]).  w_table = v2ce_pack_head_weights_f16x2 of the
  * [32][2][27] f32 weights; bias [32].  x_absmax: per batch element (desc.absmax_batch_stride) max |x| -- v2ce_absmax_batch
- * computes it -- or NULL (|x| < 4094 required); y_absmax as for v2ce_conv3d_fwd (max |y|, range-guard value). */
+ * computes it -- or NULL (|x| < 4094 required); y_absmax as for v2ce_conv3d_fwd (max |y|, range-guard value).
+ * C0 = 3 (train/main.py:203-204: --apply_image_grad adds the blurred image gradient as a third input channel) is accepted as well:
+ * x is [B][T][3][H][W0_pitch], w_table = v2ce_pack_head_weights_f16x2_c3 of the [32][3][27] f32 weights, K = 81 ordered as
+ * (channel, tap padded to 32): six k-steps, step s = channel s / 2, taps 16 (s % 2) .. + 15.  x_absmax then covers the three
+ * planes, and the range-guard value counts 81 products.  The table of one channel count is not valid for the other. */
 size_t v2ce_pack_head_weights_f16x2_bytes(void);
 int v2ce_pack_head_weights_f16x2(const float *w, void *table, v2ce_stream_t stream);
+size_t v2ce_pack_head_weights_f16x2_c3_bytes(void);
+int v2ce_pack_head_weights_f16x2_c3(const float *w, void *table, v2ce_stream_t stream);
 int v2ce_conv3d_head_f16x2(const v2ce_conv3d_desc *desc, const float *x, const void *w_table, const float *bias, float *y,
                            const float *x_absmax, float *y_absmax, v2ce_stream_t stream);
 /* slots[b * stride] = max |x[b][0 .. n)| for b < B (slots zeroed by the caller): the range slot of a network INPUT. */
@@ -651,6 +657,32 @@ int v2ce_physatt_batch(const uint8_t *frames_u8, int pair_stride, int P, int H, 
                        void *workspace, size_t workspace_bytes, v2ce_stream_t stream);
 int v2ce_log_residual_batch(const uint8_t *frames_u8, int N, int H, int W, const float *lut, float *out,
                             v2ce_stream_t stream);
+
+/* The image-gradient input channel (csrc/imgrad.hip): get_batch_double_blurred_image_gradient
+ * (train/scripts/utils/image_derivative.py:38-75) and the three-channel image units of EventPackDataset
+ * (train/scripts/data/event_pack_dataset.py:66-73) on the device.  frames_u8: uint8 [S][L + 1][H][W], S packets of L
+ * pairs (pair l of a packet = its frames l and l + 1; a clip [N][H][W] is S = 1, L = N - 1).  weights: HOST float32
+ * [kernel_size], the 1-D blur taps, read during the call and used for both passes (the reference's 2-D kernel is their
+ * outer product); kernel_size odd in [3, 15].  Arithmetic:
+ *   Gx, Gy   the Sobel sums of the uint8 pixels as integers, the frame zero-padded (F.conv2d(padding=1))
+ *   g        = sqrtf((float) max(Gx^2 + Gy^2 of frame l, of frame l + 1)) / 255.f, both correctly rounded
+ *   blur     = vertical pass of the horizontal pass of g, each  acc = fmaf(w[k], g[i - r + k], acc)  from acc = 0 for
+ *              k = 0 .. kernel_size - 1, the MAP g reflected without repeating its edge (torch 'reflect')
+ *   gmax[s]  = max of blur over packet s, as the bit pattern of the float (uint32 [S]; the entry zeroes it)
+ * v2ce_image_grad_batch writes blur f32 [S][L][H][W] and gmax_bits.  v2ce_image_units_grad writes gmax_bits and units f32
+ * [S][L][3][H][W]: channels 0 / 1 = (u8 / 255 - mean) / stdv of frames l / l + 1 in separately rounded float32
+ * operations (the bytes of v2ce_preprocess_pairs), channel 2 = blur / gmax[s], correctly rounded; a packet of black
+ * frames has gmax = 0 and a NaN channel 2, as in the reference.  workspace >= v2ce_image_grad_workspace_bytes (the
+ * blur), 4-byte aligned.  The only atomic is an integer maximum: the bytes are the same from run to run and a packet's
+ * do not depend on the other packets of the call.  S, L < 1, an even kernel_size or one outside [3, 15], H or W <=
+ * kernel_size / 2 (the reference's reflect pad raises there), sizes beyond 2^31 - 1 workgroups or a NULL pointer are
+ * V2CE_ERR_BAD_ARG, a small workspace V2CE_ERR_WORKSPACE; v2ce_image_grad_workspace_bytes returns 0 for such a shape. */
+size_t v2ce_image_grad_workspace_bytes(int S, int L, int H, int W);
+int v2ce_image_grad_batch(const uint8_t *frames_u8, int S, int L, int H, int W, const float *weights, int kernel_size,
+                          float *blur, uint32_t *gmax_bits, v2ce_stream_t stream);
+int v2ce_image_units_grad(const uint8_t *frames_u8, int S, int L, int H, int W, const float *weights, int kernel_size,
+                          float mean, float stdv, float *units, uint32_t *gmax_bits, void *workspace,
+                          size_t workspace_bytes, v2ce_stream_t stream);
 
 /* Event-frame video (csrc/event_frames.hip): the array work of write_event_frame_video (v2ce.py:253-269,275-276) on
  * the device.  mode: V2CE_EVENT_FRAMES_POLARITY = keep_polarity=True (channels S0, S1 and a zero plane, float64

@@ -15,6 +15,12 @@
 // Workgroup = 4 waves on a (4, 4, 64) output box: wave = four (t, h) rows of two 32-position fragments; halo box
 // 2 x 6 x 6 x 66 f32 in LDS.  Epilogue: bias, LeakyReLU, max |y| tracking, then the wave's fragment leaves through 4 KB of
 // wave-private LDS as lane = (position, channel quarter): four 1 KB contiguous stores of the channels-last-16 layout.
+//
+// CIN = 3 (a model built with --apply_image_grad: the two frames and the blurred image gradient, csrc/imgrad.hip) is the same
+// kernel with K ordered as (channel, tap padded to 32): 96 = six k-steps, step s carries channel s / 2, taps
+// 16 (s % 2) + 8 h + j.  A lane's eight taps now depend on its half h, so their halo offsets are sixteen per-lane
+// registers (two steps x eight taps, the same for every channel) instead of immediates; the halo box has three planes
+// (29.4 KB), the epilogue is unchanged.  The CIN = 2 instantiation keeps its table, its launch and its bytes.
 #include "conv3d_dev.h"
 
 namespace v2ce {
@@ -25,8 +31,8 @@ constexpr int kHTT = 4, kHTH = 4, kHTW = 64;                 // output box
 [[maybe_unused]] constexpr int kHPlane = kHHT * kHHH * kHPitch;               // floats per input channel
 
 struct HeadParams {
-    const float *x;              // [B][T][2][H][W0p] planar
-    const _Float16 *wt;          // table of v2ce_pack_head_weights_f16x2
+    const float *x;              // [B][T][CIN][H][W0p] planar
+    const _Float16 *wt;          // table of v2ce_pack_head_weights_f16x2 (CIN = 2) / _c3 (CIN = 3)
     const float *bias;           // [32]
     float *y;                    // [B][T][2][H][Woutp][16]
     const float *x_absmax;       // per batch element (stride amax_bs), or NULL: |x| < 4094 required
@@ -37,8 +43,11 @@ struct HeadParams {
 };
 
 #if defined(__HIP_DEVICE_COMPILE__)
+template <int CIN>
 __global__ __launch_bounds__(256) void conv3d_head_f16x2_kernel(HeadParams P) {
-    __shared__ float halo[2 * kHPlane];                       // 19.6 KB
+    static_assert(CIN == 2 || CIN == 3, "the head has two or three input channels");
+    constexpr int kSteps = CIN == 2 ? 4 : 6;                  // 16-wide k-steps
+    __shared__ float halo[CIN * kHPlane];                     // 19.6 KB / 29.4 KB
     __shared__ __attribute__((aligned(16))) float stage_all[4 * 1024];      // 4 KB per wave: the epilogue's transpose
     typedef float f32x4q __attribute__((ext_vector_type(4)));
     typedef unsigned u32x4q __attribute__((ext_vector_type(4)));
@@ -52,35 +61,35 @@ __global__ __launch_bounds__(256) void conv3d_head_f16x2_kernel(HeadParams P) {
     const int b = bid / P.nT;
     const int t0 = it * kHTT, h0 = ih * kHTH, w0 = iw * kHTW;
 
-    // A fragments of the four k-steps (the whole layer's weights: 32 registers)
-    f16x8 ah[4], al[4];
+    // A fragments of all k-steps (the whole layer's weights: 32 / 48 registers)
+    f16x8 ah[kSteps], al[kSteps];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
+    for (int s = 0; s < kSteps; ++s) {
         ah[s] = *reinterpret_cast<const f16x8 *>(P.wt + ((s * 2 + 0) * 32 + l32) * 16 + 8 * half);
         al[s] = *reinterpret_cast<const f16x8 *>(P.wt + ((s * 2 + 1) * 32 + l32) * 16 + 8 * half);
     }
-    const float *tail = reinterpret_cast<const float *>(P.wt + 4 * 2 * 32 * 16);        // { max |w|, pre-scale }
+    const float *tail = reinterpret_cast<const float *>(P.wt + kSteps * 2 * 32 * 16);   // { max |w|, pre-scale }
     const float w_scale = tail[1];
     const float amax = P.x_absmax ? P.x_absmax[b * P.amax_bs] : 4094.0f;
     const float x_scale = P.x_absmax ? pow2_prescale(amax) : kActScale;
     const float inv = 1.0f / (x_scale * w_scale);
     if (P.y_absmax && blockIdx.x == 0) {
-        // range guard of this launch (include/v2ce_hip.h): K = 54 products per output, folded scale 1
+        // range guard of this launch (include/v2ce_hip.h): K = 27 CIN products per output, folded scale 1
         for (int e = tid; e < (P.amax_bs ? P.B : 1); e += 256) {
             const float am = P.x_absmax ? P.x_absmax[e * P.amax_bs] : 4094.0f;
             const float xs = P.x_absmax ? pow2_prescale(am) : kActScale;
-            P.y_absmax[e * P.amax_bs + 1] = 54.0f * 0x1p-25f * (tail[0] / xs + am / w_scale);
+            P.y_absmax[e * P.amax_bs + 1] = (27.0f * CIN) * 0x1p-25f * (tail[0] / xs + am / w_scale);
         }
     }
 
-    // halo box: 2 x 6 x 6 rows of 66 floats, zero padded
-    const float *xb = P.x + (long long)b * P.T * 2 * (P.H * P.W0p);
-    for (int row = wave; row < 2 * kHHT * kHHH; row += 4) {
+    // halo box: CIN x 6 x 6 rows of 66 floats, zero padded
+    const float *xb = P.x + (long long)b * P.T * CIN * (P.H * P.W0p);
+    for (int row = wave; row < CIN * kHHT * kHHH; row += 4) {
         const int ci = row / (kHHT * kHHH), r = row - ci * (kHHT * kHHH);
         const int ht = r / kHHH, hh = r - ht * kHHH;
         const int t = t0 + ht - 1, h = h0 + hh - 1;
         const bool rok = t >= 0 && t < P.T && h >= 0 && h < P.H;
-        const float *src = xb + ((long long)(rok ? t : 0) * 2 + ci) * (P.H * P.W0p) + (rok ? h : 0) * P.W0p;
+        const float *src = xb + ((long long)(rok ? t : 0) * CIN + ci) * (P.H * P.W0p) + (rok ? h : 0) * P.W0p;
         float *dst = halo + ci * kHPlane + (ht * kHHH + hh) * kHPitch;
         const int w = w0 + lane - 1;
         dst[lane] = (rok && w >= 0 && w < P.W) ? src[w] : 0.0f;
@@ -99,7 +108,18 @@ __global__ __launch_bounds__(256) void conv3d_head_f16x2_kernel(HeadParams P) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) bias[r] = P.bias[(r & 3) + 8 * (r >> 2) + 4 * half];
     unsigned ymax = 0u;
-    const float *hp = halo + half * kHPlane + l32;             // this lane's channel plane, column l32
+    const float *hp = halo + (CIN == 2 ? half * kHPlane : 0) + l32;       // CIN = 2: this lane's channel plane; column l32
+    // CIN = 3: the halo offsets of this lane's taps 16 q + 8 half + j (taps >= 27 carry zero weights and read offset 0)
+    [[maybe_unused]] int toff[16];
+    if (CIN == 3) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int tap = 16 * q + 8 * half + j;
+                toff[8 * q + j] = tap < 27 ? ((tap / 9) * kHHH + (tap / 3) % 3) * kHPitch + tap % 3 : 0;
+            }
+    }
 
     // wave = rows 4 wave .. 4 wave + 3 of the box's 16 (t, h) rows, two fragments each
     for (int rr = 0; rr < 4; ++rr) {
@@ -113,16 +133,21 @@ __global__ __launch_bounds__(256) void conv3d_head_f16x2_kernel(HeadParams P) {
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-            step_loop<0, 4>([&](auto sc) {
+            step_loop<0, kSteps>([&](auto sc) {
                 constexpr int s = decltype(sc)::value;
                 float v[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const int tap = 8 * s + j;
-                    if (tap < 27) {
-                        const int dt = tap / 9, dh = (tap / 3) % 3, dw = tap % 3;
-                        v[j] = p[(dt * kHHH + dh) * kHPitch + dw];
-                    } else v[j] = 0.0f;
+                    if constexpr (CIN == 2) {
+                        const int tap = 8 * s + j;
+                        if (tap < 27) {
+                            const int dt = tap / 9, dh = (tap / 3) % 3, dw = tap % 3;
+                            v[j] = p[(dt * kHHH + dh) * kHPitch + dw];
+                        } else v[j] = 0.0f;
+                    } else {
+                        const float t = p[(s / 2) * kHPlane + toff[8 * (s % 2) + j]];
+                        v[j] = 16 * (s % 2) + 8 * half + j < 27 ? t : 0.0f;
+                    }
                 }
                 typedef unsigned u32x4c __attribute__((ext_vector_type(4)));
                 u32x4c ph, pl;
@@ -174,6 +199,7 @@ __global__ __launch_bounds__(256) void conv3d_head_f16x2_kernel(HeadParams P) {
     if (P.y_absmax) absmax_commit(__builtin_bit_cast(float, ymax), P.y_absmax + b * P.amax_bs);
 }
 #else
+template <int CIN>
 __global__ void conv3d_head_f16x2_kernel(HeadParams) {}
 #endif
 
@@ -198,6 +224,33 @@ __global__ __launch_bounds__(256) void pack_head_weights_kernel(const float *__r
     }
     if (threadIdx.x == 0) {
         float *tail = reinterpret_cast<float *>(table + 4 * 2 * 32 * 16);
+        tail[0] = red[0];
+        tail[1] = sc;
+    }
+}
+
+// CIN = 3: table[s][plane][co][8 h + j] = fp16 hi / lo of  scale * w[co][ci = s / 2][tap = 16 (s % 2) + 8 h + j]  (taps >= 27: zero),
+// six k-steps, then { max |w|, scale }
+__global__ __launch_bounds__(256) void pack_head_weights_c3_kernel(const float *__restrict__ w, _Float16 *__restrict__ table) {
+    __shared__ float red[256];
+    float m = 0.0f;
+    for (int i = threadIdx.x; i < 32 * 81; i += 256) m = fmaxf(m, fabsf(w[i]));
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int o = 128; o; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]);
+        __syncthreads();
+    }
+    const float sc = pow2_prescale(red[0]);
+    for (int e = threadIdx.x; e < 6 * 32 * 16; e += 256) {
+        const int s = e >> 9, co = (e >> 4) & 31, kk = e & 15, ci = s >> 1, tap = 16 * (s & 1) + kk;
+        const float v = tap < 27 ? w[(co * 3 + ci) * 27 + tap] * sc : 0.0f;
+        const _Float16 hi = (_Float16)v;
+        table[((s * 2 + 0) * 32 + co) * 16 + kk] = hi;
+        table[((s * 2 + 1) * 32 + co) * 16 + kk] = (_Float16)(v - (float)hi);
+    }
+    if (threadIdx.x == 0) {
+        float *tail = reinterpret_cast<float *>(table + 6 * 2 * 32 * 16);
         tail[0] = red[0];
         tail[1] = sc;
     }
@@ -247,6 +300,16 @@ extern "C" int v2ce_pack_head_weights_f16x2(const float *w, void *table, v2ce_st
     return V2CE_OK;
 }
 
+extern "C" size_t v2ce_pack_head_weights_f16x2_c3_bytes(void) { return 6 * 2 * 32 * 16 * 2 + 16; }
+
+extern "C" int v2ce_pack_head_weights_f16x2_c3(const float *w, void *table, v2ce_stream_t stream) {
+    clear_error();
+    V2CE_REQUIRE(w && table, V2CE_ERR_BAD_ARG, "v2ce_pack_head_weights_f16x2_c3: null pointer");
+    hipLaunchKernelGGL(pack_head_weights_c3_kernel, dim3(1), dim3(256), 0, as_stream(stream), w, static_cast<_Float16 *>(table));
+    V2CE_HIP_CHECK(hipGetLastError());
+    return V2CE_OK;
+}
+
 extern "C" int v2ce_absmax_batch(const float *x, int B, long long n, float *slots, int stride, v2ce_stream_t stream) {
     clear_error();
     V2CE_REQUIRE(x && slots && B > 0 && n > 0 && stride >= 1, V2CE_ERR_BAD_ARG, "v2ce_absmax_batch: bad argument");
@@ -262,9 +325,9 @@ extern "C" int v2ce_conv3d_head_f16x2(const v2ce_conv3d_desc *desc, const float 
     clear_error();
     V2CE_REQUIRE(desc && x && w_table && bias && y, V2CE_ERR_BAD_ARG, "v2ce_conv3d_head_f16x2: null pointer");
     const v2ce_conv3d_desc &d = *desc;
-    V2CE_REQUIRE(d.B > 0 && d.T > 0 && d.C0 == 2 && d.C1 == 0 && d.Cout == 32 && d.ksize == 3 && d.stride_hw == 1 && d.H0 == d.Hin &&
+    V2CE_REQUIRE(d.B > 0 && d.T > 0 && (d.C0 == 2 || d.C0 == 3) && d.C1 == 0 && d.Cout == 32 && d.ksize == 3 && d.stride_hw == 1 && d.H0 == d.Hin &&
                  d.W0 == d.Win && d.Hout == d.Hin && d.Wout == d.Win && d.layout == V2CE_LAYOUT_C16, V2CE_ERR_UNSUPPORTED,
-                 "v2ce_conv3d_head_f16x2: the UNet's head is a 3x3x3 stride-1 conv of 2 planar input channels into 32 channels-last-16 ones");
+                 "v2ce_conv3d_head_f16x2: the UNet's head is a 3x3x3 stride-1 conv of 2 or 3 planar input channels into 32 channels-last-16 ones");
     V2CE_REQUIRE(d.act == V2CE_ACT_LEAKY || d.act == V2CE_ACT_RELU || d.act == V2CE_ACT_NONE, V2CE_ERR_BAD_ARG, "v2ce_conv3d_head_f16x2: act %d", d.act);
     const int W0p = d.W0_pitch > 0 ? d.W0_pitch : d.W0, Woutp = d.Wout_pitch > 0 ? d.Wout_pitch : d.Wout;
     V2CE_REQUIRE(W0p >= d.W0 && Woutp >= d.Wout, V2CE_ERR_BAD_ARG, "v2ce_conv3d_head_f16x2: a row pitch is smaller than its width");
@@ -279,7 +342,10 @@ extern "C" int v2ce_conv3d_head_f16x2(const v2ce_conv3d_desc *desc, const float 
     P.per_xcd = (P.n_spatial + 7) / 8;
     P.slope = d.act == V2CE_ACT_RELU ? 0.0f : (d.act == V2CE_ACT_LEAKY ? 0.01f : 1.0f);
     V2CE_REQUIRE((long long)P.n_spatial < (1ll << 28), V2CE_ERR_UNSUPPORTED, "v2ce_conv3d_head_f16x2: too many boxes");
-    hipLaunchKernelGGL(conv3d_head_f16x2_kernel, dim3((unsigned)(8 * P.per_xcd)), dim3(256), 0, as_stream(stream), P);
+    if (d.C0 == 2)
+        hipLaunchKernelGGL(conv3d_head_f16x2_kernel<2>, dim3((unsigned)(8 * P.per_xcd)), dim3(256), 0, as_stream(stream), P);
+    else
+        hipLaunchKernelGGL(conv3d_head_f16x2_kernel<3>, dim3((unsigned)(8 * P.per_xcd)), dim3(256), 0, as_stream(stream), P);
     V2CE_HIP_CHECK(hipGetLastError());
     return V2CE_OK;
 }

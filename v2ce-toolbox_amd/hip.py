@@ -34,11 +34,13 @@ EXPORTS = [
     "v2ce_conv3d_fwd_up2", "v2ce_pack_weights_f16x2_up", "v2ce_pack_weights_f16x2_up_bytes", "v2ce_conv3d_up2_variant",
     "v2ce_conv3d_fwd_wt", "v2ce_conv3d_fwd_wt_tail", "v2ce_pack_weights_f16x2_wt", "v2ce_pack_weights_f16x2_wt_slice", "v2ce_conv3d_fwd_up2_part", "v2ce_pack_weights_f16x2_wt_bytes", "v2ce_conv3d_wt_variant",
     "v2ce_conv3d_head_f16x2", "v2ce_pack_head_weights_f16x2", "v2ce_pack_head_weights_f16x2_bytes", "v2ce_absmax_batch",
+    "v2ce_pack_head_weights_f16x2_c3", "v2ce_pack_head_weights_f16x2_c3_bytes",
     "v2ce_tsdiff_workspace_bytes", "v2ce_tsdiff",
     "v2ce_voxmetrics_workspace_bytes", "v2ce_voxmetrics", "v2ce_voxelize_batch_workspace_bytes", "v2ce_voxelize_batch",
     "v2ce_event_frames_hist_bytes", "v2ce_event_frames_sums", "v2ce_event_frames_refine", "v2ce_event_frames_render",
     "v2ce_event_grids_workspace_bytes", "v2ce_event_grids_batch",
     "v2ce_physatt_workspace_bytes", "v2ce_physatt_batch", "v2ce_log_residual_batch",
+    "v2ce_image_grad_workspace_bytes", "v2ce_image_grad_batch", "v2ce_image_units_grad",
 ]
 
 
@@ -209,6 +211,10 @@ def lib() -> ctypes.CDLL:
     L.v2ce_pack_head_weights_f16x2.restype = ctypes.c_int
     L.v2ce_pack_head_weights_f16x2_bytes.argtypes = []
     L.v2ce_pack_head_weights_f16x2_bytes.restype = sz
+    L.v2ce_pack_head_weights_f16x2_c3.argtypes = [vp, vp, vp]
+    L.v2ce_pack_head_weights_f16x2_c3.restype = ctypes.c_int
+    L.v2ce_pack_head_weights_f16x2_c3_bytes.argtypes = []
+    L.v2ce_pack_head_weights_f16x2_c3_bytes.restype = sz
     L.v2ce_absmax_batch.argtypes = [vp, i32, ctypes.c_longlong, vp, i32, vp]
     L.v2ce_absmax_batch.restype = ctypes.c_int
     L.v2ce_pack_pred_weights_f16x2.argtypes = [vp, i32, i32, vp, vp]
@@ -254,6 +260,13 @@ def lib() -> ctypes.CDLL:
     L.v2ce_physatt_batch.restype = ctypes.c_int
     L.v2ce_log_residual_batch.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.v2ce_log_residual_batch.restype = ctypes.c_int
+    fp = ctypes.POINTER(ctypes.c_float)
+    L.v2ce_image_grad_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    L.v2ce_image_grad_workspace_bytes.restype = sz
+    L.v2ce_image_grad_batch.argtypes = [vp, i32, i32, i32, i32, fp, i32, vp, vp, vp]
+    L.v2ce_image_grad_batch.restype = ctypes.c_int
+    L.v2ce_image_units_grad.argtypes = [vp, i32, i32, i32, i32, fp, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, sz, vp]
+    L.v2ce_image_units_grad.restype = ctypes.c_int
     L.v2ce_event_frames_hist_bytes.argtypes = [i32]
     L.v2ce_event_frames_hist_bytes.restype = sz
     L.v2ce_event_frames_sums.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]

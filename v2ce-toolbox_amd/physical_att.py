@@ -8,7 +8,7 @@
 * ``gen_log_frame_residual(frames)`` / ``gen_log_frame_residual_batch(frames)``         :216-247  float32 ``[N-1, 1, H, W]``
 * ``physical_attention_batch(frames, events, counts, ...)``  P frame pairs and their events in one call
 * ``packet_physical_att(images, events, counts)``  the call of ``train/scripts/tools/gen_phy_att.py:25``
-* ``main()``  the command line (``v2ce_prep.py``)
+* ``main()``  the command line (``v2ce_prep.py``; ``--image_grad`` adds the image units of ``image_derivative``)
 
 ``Hp = ceil(H / pool_size)``, ``Wp = ceil(W / pool_size)`` (skimage's ``block_reduce`` pads with zeros).  Everything runs
 ``v2ce_physatt_batch`` / ``v2ce_log_residual_batch`` (``csrc/physatt.hip``), whose arithmetic follows NumPy's and SciPy's
@@ -302,6 +302,11 @@ def build_parser():
     p.add_argument("--ceiling", type=float, default=25)
     p.add_argument("--mode", type=str, default="advanced", choices=["plain", "advanced"])
     p.add_argument("--chunk", type=int, default=64, help="frame pairs per device call")
+    p.add_argument("--image_grad", action="store_true",
+                   help="also write the three-channel image units of --apply_image_grad (image_units.npy, image_grad_max.npy)")
+    p.add_argument("--seq_len", type=int, default=16, help="with --image_grad: frame pairs per packet (the gradient channel "
+                                                           "is normalised by its packet's maximum); whole packets of "
+                                                           "about --chunk pairs go through the device at a time")
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("-o", "--out_folder", type=str, default="./results")
     p.add_argument("-l", "--log_level", type=str, default="info")
@@ -310,7 +315,8 @@ def build_parser():
 
 def main(argv=None):
     """Writes ``physical_att.npy`` float32 [N-1, Hp, Wp], ``lfr.npy`` float32 [N-1, 1, H, W] and ``status.npy`` (int32 per
-    pair).  A pair with coordinates outside the frame stops the command."""
+    pair).  A pair with coordinates outside the frame stops the command.  With ``--image_grad`` also ``image_units.npy``
+    float32 [N-1, 3, H, W] and ``image_grad_max.npy`` float32 [ceil((N-1) / seq_len)] (``image_derivative.clip_image_units``)."""
     from . import glue
     from .stage2_metrics import load_events, split_by_frames
     args = build_parser().parse_args(argv)
@@ -350,6 +356,20 @@ def main(argv=None):
     for name, parts in (("physical_att", maps), ("lfr", lfr), ("status", status)):
         np.save(op.join(args.out_folder, f"{name}.npy"), np.concatenate(parts))
         print(op.join(args.out_folder, f"{name}.npy"))
+    if args.image_grad:
+        from .image_derivative import clip_image_units
+        if args.seq_len < 1:
+            raise SystemExit(f"--seq_len must be positive, got {args.seq_len}")
+        # whole packets per device call, about --chunk pairs: the device holds one piece's units at a time
+        step = max(1, args.chunk // args.seq_len) * args.seq_len
+        units, gmax = [], []
+        for c0 in range(0, N - 1, step):
+            u, g = clip_image_units(frames[c0:c0 + step + 1], seq_len=args.seq_len)
+            units.append(u.cpu().numpy())
+            gmax.append(g.cpu().numpy())
+        for name, parts in (("image_units", units), ("image_grad_max", gmax)):
+            np.save(op.join(args.out_folder, f"{name}.npy"), np.concatenate(parts))
+            print(op.join(args.out_folder, f"{name}.npy"))
 
 
 if __name__ == "__main__":

@@ -242,11 +242,15 @@ class V2ce3d(nn.Module):
         h = self.UNet.head.conv3d
         P["head"] = (self._pack(h.weight.contiguous()), ones(h.weight.shape[0]), h.bias.float().contiguous())
         P["head_split"] = None
-        if self.precision == "f16x2" and tuple(h.weight.shape) == (32, 2, 3, 3, 3) and os.environ.get("V2CE_HEAD_SPLIT", "1") != "0":
-            # the head in split-half arithmetic like every other layer (v2ce_conv3d_head_f16x2: a stream of 1 KB stores)
-            tab = torch.empty(hip.lib().v2ce_pack_head_weights_f16x2_bytes() // 2, dtype=torch.float16, device=dev)
-            hip.check(hip.lib().v2ce_pack_head_weights_f16x2(h.weight.contiguous().data_ptr(), tab.data_ptr(), hip.stream_ptr(dev)),
-                      "v2ce_pack_head_weights_f16x2")
+        if (self.precision == "f16x2" and tuple(h.weight.shape) in ((32, 2, 3, 3, 3), (32, 3, 3, 3, 3))
+                and os.environ.get("V2CE_HEAD_SPLIT", "1") != "0"):
+            # the head in split-half arithmetic like every other layer (v2ce_conv3d_head_f16x2: a stream of 1 KB stores); three input
+            # channels (--apply_image_grad: image_derivative.image_units_batch) have their own table order
+            sfx = "_c3" if h.weight.shape[1] == 3 else ""
+            tab = torch.empty(getattr(hip.lib(), f"v2ce_pack_head_weights_f16x2{sfx}_bytes")() // 2, dtype=torch.float16, device=dev)
+            hip.check(getattr(hip.lib(), f"v2ce_pack_head_weights_f16x2{sfx}")(h.weight.contiguous().data_ptr(), tab.data_ptr(),
+                                                                                hip.stream_ptr(dev)),
+                      f"v2ce_pack_head_weights_f16x2{sfx}")
             P["head_split"] = (tab, h.bias.float().contiguous())
         pr = self.UNet.pred.conv3d
         P["pred"] = (self._pack(pr.weight.contiguous()), ones(pr.weight.shape[0]), pr.bias.float().contiguous())
@@ -697,7 +701,7 @@ class V2ce3d(nn.Module):
     def _head_split(self, x, table, bias):
         """The head convolution on the split-half kernel: max |x| per sequence into a range slot (v2ce_absmax_batch), then
         v2ce_conv3d_head_f16x2 -- planar network input in, channels-last-16 activations out."""
-        B, T, _, H, W = x.shape
+        B, T, C, H, W = x.shape                                   # C = 2, or 3 with the c3 table
         Wp = self._pitch(W)
         y = torch.empty((B, T, 2, H, Wp, 16), dtype=torch.float32, device=x.device)
         y.lw, y.c16 = W, True
@@ -706,12 +710,12 @@ class V2ce3d(nn.Module):
         ay = y.absmax = self._prep["absmax"][self._slot + 1]
         self._slot += 2
         st = hip.stream_ptr(x.device)
-        n = T * 2 * H * W
+        n = T * C * H * W
         if per_b:
             hip.check(hip.lib().v2ce_absmax_batch(x.data_ptr(), B, n, ax.data_ptr(), 2, st), "v2ce_absmax_batch")
         else:
             hip.check(hip.lib().v2ce_absmax_batch(x.data_ptr(), 1, B * n, ax.data_ptr(), 2, st), "v2ce_absmax_batch")
-        d = hip.ConvDesc(B=B, T=T, C0=2, H0=H, W0=W, C1=0, Hin=H, Win=W, Cout=32, Hout=H, Wout=W, ksize=3, stride_hw=1,
+        d = hip.ConvDesc(B=B, T=T, C0=C, H0=H, W0=W, C1=0, Hin=H, Win=W, Cout=32, Hout=H, Wout=W, ksize=3, stride_hw=1,
                          act=hip.ACT_LEAKY, tile_t=0, tile_h=0, tile_w=0, precision=hip.PRECISION_F16X2, W0_pitch=W, Win_pitch=W,
                          Wout_pitch=Wp, layout=hip.LAYOUT_C16, absmax_batch_stride=2 if per_b else 0)
         prof = self._prof_list()
@@ -722,7 +726,7 @@ class V2ce3d(nn.Module):
                                                    ax.data_ptr(), ay.data_ptr(), st), "v2ce_conv3d_head_f16x2")
         if prof is not None:
             e1.record()
-            flops = 2.0 * B * T * H * W * 32 * 54
+            flops = 2.0 * B * T * H * W * 32 * 27 * C
             prof.append(("conv3d_head_f16x2_kernel", flops, e0, e1, flops))
         return y
 
