@@ -457,8 +457,9 @@ int v2ce_voxelize_events(const int64_t *ts, const int16_t *x, const int16_t *y, 
  * u_bern < frac(y)); V2CE_RNG_PHILOX draws them from Philox4x32-10, counter (pixel, j >> 2, 32*kind + 10*P + c,
  * frame_base + b), kind 0 / 1 / 2 = u_int / u_dec / u_bern, key = seed.  _EVEN reads u_bern only.
  * Two-phase like LDATI: count -> the caller reads frame_counts [B] (int64, device) and max_int, allocates the SoA
- * outputs and the workspace -> emit.  status [1] (device int32) != 0: a timestamp fell outside the frame's key range
- * (NaN or inf from a degenerate slope; the reference's output is platform-defined there). */
+ * outputs and the workspace -> emit.  status [1] (device int32) != 0: a timestamp is not finite (decided on the f32
+ * time, before its cast to int64) or fell outside the frame's key range (NaN or inf from a degenerate slope or a negative
+ * voxel; the reference's output is platform-defined there): the events of the call must be discarded. */
 #define V2CE_SAMPLER_RANDOM 0
 #define V2CE_SAMPLER_EVEN 1
 #define V2CE_SAMPLER_PURE_SLOPE 2

@@ -43,13 +43,17 @@ def offsets(fps: float, t0: float) -> np.ndarray:
     return (np.arange(C, dtype=np.float64) * step).astype(F) + F(t0)
 
 
-def _to_us(ts: np.ndarray, off: np.ndarray, axis: int) -> np.ndarray:
+def _us_f32(ts: np.ndarray, off: np.ndarray, axis: int) -> np.ndarray:
     shape = [1] * ts.ndim
     shape[axis] = C
-    ts = ts + off.reshape(shape)                 # ts += arange + t0
-    ts = ts * F(1e6)                             # ts *= 1e6
+    with np.errstate(invalid="ignore", over="ignore"):
+        ts = ts + off.reshape(shape)             # ts += arange + t0
+        return ts * F(1e6)                       # ts *= 1e6
+
+
+def _to_us(us: np.ndarray) -> np.ndarray:
     with np.errstate(invalid="ignore"):
-        return ts.astype(np.int64)               # .to(torch.long): truncation
+        return us.astype(np.int64)               # .to(torch.long): truncation
 
 
 def _collect(ts_int, n_int, ts_dec, sel_dec):
@@ -82,8 +86,8 @@ def _collect(ts_int, n_int, ts_dec, sel_dec):
     return out
 
 
-def sample_voxel_baseline(y, t0=0, fps=30, even=False, random=False, u_int=None, u_dec=None, u_bern=None):
-    """random_even_sample.py:115-169.  ``even`` wins when both flags are set (its assignment comes second)."""
+def _baseline_parts(y, t0, fps, even, random, u_int, u_dec, u_bern):
+    """-> (f32 microsecond times of the floor events [B,2,10,H,W,M], floor(y), those of the Bernoulli events, their selection)"""
     assert even or random                                                   # :116
     y = np.asarray(y, dtype=F)
     B, P, Cc, H, W = y.shape
@@ -94,18 +98,21 @@ def sample_voxel_baseline(y, t0=0, fps=30, even=False, random=False, u_int=None,
     M = int(ip.max()) if ip.size else 0                                     # :129
     off = offsets(fps, t0)
     if even:
-        j = np.arange(M, dtype=F)
-        ts = (j / (ip[..., None] + F(1))) * delta                           # :138-140
+        j = np.arange(max(M, 0), dtype=F)
+        with np.errstate(divide="ignore", invalid="ignore"):                # floor(y) == -1: j / 0 (never selected) and -1 / 0
+            ts = (j / (ip[..., None] + F(1))) * delta                       # :138-140
+            td = (ip / (ip + F(1))) * delta                                 # :152-153
     else:
-        ts = np.asarray(u_int, F).reshape(B, P, C, H, W, -1)[..., :M] * delta   # :134
-    ts_int = _to_us(ts, off, 2)                                             # :143-145
-    if even:
-        td = (ip / (ip + F(1))) * delta                                     # :152-153
-    else:
+        ts = np.asarray(u_int, F).reshape(B, P, C, H, W, -1)[..., :max(M, 0)] * delta   # :134
         td = np.asarray(u_dec, F).reshape(B, P, C, H, W) * delta            # :149
-    ts_dec = _to_us(td, off, 2)                                             # :156-158
     sel = np.asarray(u_bern, F).reshape(B, P, C, H, W) < dp                 # :53 (bernoulli)
-    return _collect(ts_int, ip, ts_dec, sel)
+    return _us_f32(ts, off, 2), ip, _us_f32(td, off, 2), sel                # :143-144, :156-157
+
+
+def sample_voxel_baseline(y, t0=0, fps=30, even=False, random=False, u_int=None, u_dec=None, u_bern=None):
+    """random_even_sample.py:115-169.  ``even`` wins when both flags are set (its assignment comes second)."""
+    us_int, ip, us_dec, sel = _baseline_parts(y, t0, fps, even, random, u_int, u_dec, u_bern)
+    return _collect(_to_us(us_int), ip, _to_us(us_dec), sel)                # :145, :158
 
 
 def _slope_kb(y, fps):
@@ -152,13 +159,9 @@ def pool_voxels(y, pooling_type, pooling_kernel_size=3):
     return acc if pooling_type == "weighted" else acc / F(pooling_kernel_size * pooling_kernel_size)
 
 
-def sample_voxel_pure_slope(y, t0=0, fps=30, pooling_type="none", pooling_kernel_size=3,
-                            additional_events_strategy="slope", u_int=None, u_dec=None, u_bern=None):
-    """pure_slope_sample.py:57-149.  Does not modify ``y`` (the reference folds bin 9 into bin 8 in place, :92-93,
-    which reaches the caller's tensor).  Pooling shapes only the slope parameters (:79-91, from the UNFOLDED values);
-    the event counts come from ``y`` itself."""
+def _pure_slope_parts(y, t0, fps, pooling_type, pooling_kernel_size, u_int, u_dec, u_bern):
+    """-> (f32 microsecond times of the floor events [B,2,10,H,W,M], floor(y), those of the Bernoulli events, their selection)"""
     assert pooling_type in ["avg", "weighted", "none"]
-    assert additional_events_strategy in ["none", "random", "slope"]
     y = np.array(y, dtype=F)
     B, P, Cc, H, W = y.shape
     assert Cc == C
@@ -168,12 +171,35 @@ def sample_voxel_pure_slope(y, t0=0, fps=30, pooling_type="none", pooling_kernel
     ip = np.floor(y).astype(np.int32)                                       # :95
     dp = y - ip.astype(F)                                                   # :96
     off = offsets(fps, t0)
-    ts_dec = _to_us(_slope_ts(k, bb, np.asarray(u_dec, F).reshape(B, P, C, H, W), fps), off, 2)   # :100-112
+    us_dec = _us_f32(_slope_ts(k, bb, np.asarray(u_dec, F).reshape(B, P, C, H, W), fps), off, 2)   # :100-111
     sel = np.asarray(u_bern, F).reshape(B, P, C, H, W) < dp
-    M = int(ip.max()) if ip.size else 0                                     # :117
+    M = max(int(ip.max()), 0) if ip.size else 0                             # :117
     u = np.asarray(u_int, F).reshape(B, P, C, H, W, -1)[..., :M]
-    ts_int = _to_us(_slope_ts(k[..., None], bb[..., None], u, fps), off, 2)  # :121-140
-    return _collect(ts_int, ip, ts_dec, sel)
+    us_int = _us_f32(_slope_ts(k[..., None], bb[..., None], u, fps), off, 2)  # :121-137
+    return us_int, ip, us_dec, sel
+
+
+def sample_voxel_pure_slope(y, t0=0, fps=30, pooling_type="none", pooling_kernel_size=3,
+                            additional_events_strategy="slope", u_int=None, u_dec=None, u_bern=None):
+    """pure_slope_sample.py:57-149.  Does not modify ``y`` (the reference folds bin 9 into bin 8 in place, :92-93,
+    which reaches the caller's tensor).  Pooling shapes only the slope parameters (:79-91, from the UNFOLDED values);
+    the event counts come from ``y`` itself."""
+    assert additional_events_strategy in ["none", "random", "slope"]
+    us_int, ip, us_dec, sel = _pure_slope_parts(y, t0, fps, pooling_type, pooling_kernel_size, u_int, u_dec, u_bern)
+    return _collect(_to_us(us_int), ip, _to_us(us_dec), sel)                # :112, :138
+
+
+def selected_times_us(y, kind, mode, t0=0, fps=30, pooling_type="none", pooling_kernel_size=3, u_int=None, u_dec=None,
+                      u_bern=None):
+    """The f32 times, in microseconds and BEFORE the cast to int64, of the events a call emits: those of the floor(y)
+    events, then those of the Bernoulli events.  The cast of a NaN, an inf or a value beyond int64 is
+    platform-defined, in the reference as well; tests read here whether a call has a defined result at all."""
+    if kind == "baseline":
+        us_int, ip, us_dec, sel = _baseline_parts(y, t0, fps, mode == "even", mode == "random", u_int, u_dec, u_bern)
+    else:
+        us_int, ip, us_dec, sel = _pure_slope_parts(y, t0, fps, pooling_type, pooling_kernel_size, u_int, u_dec, u_bern)
+    pick = np.arange(us_int.shape[-1]) < ip[..., None]
+    return np.concatenate([us_int[pick], us_dec[sel]])
 
 
 def philox_draws(B, H, W, M, seed, frame_base=0):

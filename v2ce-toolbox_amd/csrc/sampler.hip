@@ -92,10 +92,11 @@ __device__ __forceinline__ void split_voxel(const SamplerParams &P, const float 
     dp = v - ip;                                            // :126 / pure_slope :96
 }
 
-__device__ __forceinline__ long long to_us(float t, float off) {
+// the reference's time in microseconds as it stands before .to(torch.long): ts += arange + t0; ts *= 1e6
+__device__ __forceinline__ float to_us(float t, float off) {
     t = t + off;
     t = t * 1e6f;
-    return (long long)t;
+    return t;
 }
 
 struct Slope {
@@ -201,8 +202,12 @@ __global__ __launch_bounds__(256) void sampler_emit_kernel(SamplerParams P) {
     const int tshift = P.xb + P.yb + 1;
     const unsigned long long fbits = (unsigned long long)b << (P.tb + tshift);
     bool bad = false;
-    auto put = [&](long long ts) {
-        long long rel = ts - P.ts_base;
+    // The cast of a NaN, an inf or a value beyond int64 has no defined result (a NaN came out as 0, which lies INSIDE the
+    // window of a frame near t0 = 0): such a time is refused on the float, before the cast; every other time is cast as
+    // before.  4e18 leaves room for ts_base below the int64 range.
+    auto put = [&](float us) {
+        const bool castable = us > -4.0e18f && us < 4.0e18f;         // false for NaN
+        long long rel = castable ? (long long)us - P.ts_base : (us > 0.0f ? (1ll << P.tb) : -1ll);
         if (rel < 0 || rel >= (1ll << P.tb)) {
             bad = true;
             rel = rel < 0 ? 0 : (1ll << P.tb) - 1;

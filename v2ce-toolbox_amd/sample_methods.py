@@ -119,8 +119,8 @@ def sampler_device(y: torch.Tensor, mode: int, t0=0, fps=30, *, rng: str = "phil
                                       hip.ptr(p), ws.data_ptr(), ws.numel(), status.data_ptr(), st), "v2ce_sampler_emit")
         ev = DeviceEvents(None, counts.reshape(B, 1), max_int, soa=(ts, x, yy, p))
         ev._status = status
-        ev._status_message = ("sample_methods: a timestamp left its frame's range (NaN / inf from a degenerate slope; "
-                              "the reference's value is platform-defined there)")
+        ev._status_message = ("sample_methods: a timestamp is not finite or left its frame's range (NaN / inf from a "
+                              "degenerate slope or a negative voxel; the reference's value is platform-defined there)")
         ws.record_stream(torch.cuda.current_stream(dev))
         for t in keep:
             t.record_stream(torch.cuda.current_stream(dev))
