@@ -546,6 +546,59 @@ int v2ce_voxmetrics(const float *pred, const float *gt, int B, int L, int C, int
                     const int *pool_sizes, int n_pools, v2ce_voxmetrics_stats *stats, size_t stats_struct_size,
                     void *workspace, size_t workspace_bytes, v2ce_stream_t stream);
 
+/* Stage-1 loss terms (csrc/voxlosses.hip): the voxel-only terms of ModelInterface.calculate_loss and the classes of
+ * train/scripts/model/losses.py as sufficient statistics -- f64 sums and int64 counts that combine across records by
+ * addition.  v2ce_voxlosses takes pred, gt [B][L][C][H][W] f32 (C must be 20, channels (p c)), contiguous, on the device,
+ * and writes one record per sequence b; v2ce_volume_losses takes [N][D][H][W] (what the reference's rearrange
+ * 'b l (p c) h w -> (b p) (l c) h w' hands to Pyramid3dLoss / PyramidTemporalLoss) and writes one record per volume n
+ * with the elementwise, pyramid and temporal fields only.  The 5-D record of b equals the sum of the records of its two
+ * volumes (b, p) bit for bit.
+ *   n, sq_sum = sum (p - g)^2, abs_diff_sum, pred_abs_sum = sum |p|, pred_sq_sum = sum p^2: always written
+ *   V2CE_VOXLOSSES_PYRAMID  pyr_sq_sum[q] = sum (pool_k(p) - pool_k(g))^2, k = 2, 4, 8, pool_k = AvgPool3d(k, stride k)
+ *       over (D, H, W) of one volume, each axis floored to a multiple of k; needs min(D, H, W) >= 8
+ *   V2CE_VOXLOSSES_TEMPORAL  per volume and pixel along D: [0] AvgPool1d(3, stride 3, padding 1) (divisor always 3,
+ *       (D - 1) / 3 + 1 values), [1] AvgPool1d(5, stride 5) (D / 5 values); needs D >= 5
+ *   V2CE_VOXLOSSES_EF  squared differences of event frames of |v|: [0] the 20 channels summed -> [L][H][W], [1] channels
+ *       and frames -> [H][W], [2] the 10 bins per polarity -> [L][2][H][W], [3] bins and frames -> [2][H][W]
+ *   V2CE_VOXLOSSES_COMPENSATION  per (l, w): (mean_p - mean_g)^2 with mean = sum over (c, h) of v * (v > 0.01f) divided
+ *       by max(count of v > 0.01f, 1): CompensationLoss on a 5-D input, whose dim = (2, 3) reduces channels and rows
+ *   V2CE_VOXLOSSES_MATCH  per (c, h, w) over l: logsumexp_l(pred) - pred[t], t = the first argmax_l of gt; match_low
+ *       counts the columns with pred[t] - max_l pred < -80, where the reference's f32 softmax has underflowed
+ * Every difference, product, mean, exp and log is f64 from the f32 inputs; v > 0.01f is an f32 compare.  A field whose
+ * term was not requested is zero.  No float atomics: records are bit-identical run to run and do not depend on B / N.
+ * stats_struct_size must be sizeof(v2ce_voxlosses_stats).  Workspace >= the *_workspace_bytes value, which is 0 for
+ * arguments the entry refuses. */
+#define V2CE_VOXLOSSES_PYRAMID 1
+#define V2CE_VOXLOSSES_TEMPORAL 2
+#define V2CE_VOXLOSSES_EF 4
+#define V2CE_VOXLOSSES_COMPENSATION 8
+#define V2CE_VOXLOSSES_MATCH 16
+typedef struct v2ce_voxlosses_stats {
+    int64_t struct_size;
+    int64_t term_mask;
+    int64_t n;
+    double sq_sum, abs_diff_sum, pred_abs_sum, pred_sq_sum;
+    int64_t pyr_n[3];
+    double pyr_sq_sum[3];
+    int64_t temporal_n[2];
+    double temporal_sq_sum[2];
+    int64_t ef_n[4];
+    double ef_sq_sum[4];
+    int64_t comp_n;
+    double comp_sq_sum;
+    int64_t match_n;
+    double match_sum;
+    int64_t match_low;
+} v2ce_voxlosses_stats;
+size_t v2ce_voxlosses_workspace_bytes(int B, int L, int C, int H, int W, int term_mask);
+int v2ce_voxlosses(const float *pred, const float *gt, int B, int L, int C, int H, int W, int term_mask,
+                   v2ce_voxlosses_stats *stats, size_t stats_struct_size, void *workspace, size_t workspace_bytes,
+                   v2ce_stream_t stream);
+size_t v2ce_volume_losses_workspace_bytes(int N, int D, int H, int W, int term_mask);
+int v2ce_volume_losses(const float *pred, const float *gt, int N, int D, int H, int W, int term_mask,
+                       v2ce_voxlosses_stats *stats, size_t stats_struct_size, void *workspace, size_t workspace_bytes,
+                       v2ce_stream_t stream);
+
 /* Batched, deterministic voxeliser (csrc/voxelize.hip): P event lists -> volume [P][2*bins][H][W] f32.  Events are SoA
  * (timestamp int64, x, y int16, polarity int8); pair i owns events [offsets[i], offsets[i+1]) (int64 [P+1], monotone,
  * within [0, n]).  Per pair the time range is its own [t_min, t_max], or t_range[i] = {t_min, t_max} (int64 [P][2],

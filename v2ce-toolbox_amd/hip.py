@@ -36,6 +36,7 @@ EXPORTS = [
     "v2ce_conv3d_head_f16x2", "v2ce_pack_head_weights_f16x2", "v2ce_pack_head_weights_f16x2_bytes", "v2ce_absmax_batch",
     "v2ce_pack_head_weights_f16x2_c3", "v2ce_pack_head_weights_f16x2_c3_bytes",
     "v2ce_tsdiff_workspace_bytes", "v2ce_tsdiff",
+    "v2ce_voxlosses_workspace_bytes", "v2ce_voxlosses", "v2ce_volume_losses_workspace_bytes", "v2ce_volume_losses",
     "v2ce_voxmetrics_workspace_bytes", "v2ce_voxmetrics", "v2ce_voxelize_batch_workspace_bytes", "v2ce_voxelize_batch",
     "v2ce_event_frames_hist_bytes", "v2ce_event_frames_sums", "v2ce_event_frames_refine", "v2ce_event_frames_render",
     "v2ce_event_grids_workspace_bytes", "v2ce_event_grids_batch",
@@ -91,6 +92,20 @@ class VoxMetricsStats(ctypes.Structure):
                 ("ratio_sum", ctypes.c_double), ("n_pools", ctypes.c_int64),
                 ("pool_size", ctypes.c_int64 * VOXMETRICS_MAX_POOLS), ("pool_n", ctypes.c_int64 * VOXMETRICS_MAX_POOLS),
                 ("pool_sq_sum", ctypes.c_double * VOXMETRICS_MAX_POOLS)]
+
+
+VOXLOSSES_PYRAMID, VOXLOSSES_TEMPORAL, VOXLOSSES_EF, VOXLOSSES_COMPENSATION, VOXLOSSES_MATCH = 1, 2, 4, 8, 16
+
+
+class VoxLossesStats(ctypes.Structure):
+    """``v2ce_voxlosses_stats`` (include/v2ce_hip.h): the stage-1 loss statistics of one sequence or volume."""
+    _fields_ = [("struct_size", ctypes.c_int64), ("term_mask", ctypes.c_int64), ("n", ctypes.c_int64),
+                ("sq_sum", ctypes.c_double), ("abs_diff_sum", ctypes.c_double), ("pred_abs_sum", ctypes.c_double),
+                ("pred_sq_sum", ctypes.c_double), ("pyr_n", ctypes.c_int64 * 3), ("pyr_sq_sum", ctypes.c_double * 3),
+                ("temporal_n", ctypes.c_int64 * 2), ("temporal_sq_sum", ctypes.c_double * 2),
+                ("ef_n", ctypes.c_int64 * 4), ("ef_sq_sum", ctypes.c_double * 4), ("comp_n", ctypes.c_int64),
+                ("comp_sq_sum", ctypes.c_double), ("match_n", ctypes.c_int64), ("match_sum", ctypes.c_double),
+                ("match_low", ctypes.c_int64)]
 
 
 VOXELIZE_EMPTY, VOXELIZE_SINGLE_TIMESTAMP, VOXELIZE_BAD_XY, VOXELIZE_BAD_RANGE = 1, 2, 4, 8
@@ -245,6 +260,14 @@ def lib() -> ctypes.CDLL:
     L.v2ce_voxmetrics_workspace_bytes.restype = sz
     L.v2ce_voxmetrics.argtypes = [vp, vp, i32, i32, i32, i32, i32, ctypes.c_float, vp, i32, vp, sz, vp, sz, vp]
     L.v2ce_voxmetrics.restype = ctypes.c_int
+    L.v2ce_voxlosses_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32]
+    L.v2ce_voxlosses_workspace_bytes.restype = sz
+    L.v2ce_voxlosses.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]
+    L.v2ce_voxlosses.restype = ctypes.c_int
+    L.v2ce_volume_losses_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+    L.v2ce_volume_losses_workspace_bytes.restype = sz
+    L.v2ce_volume_losses.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]
+    L.v2ce_volume_losses.restype = ctypes.c_int
     L.v2ce_voxelize_batch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
     L.v2ce_voxelize_batch_workspace_bytes.restype = sz
     L.v2ce_voxelize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]

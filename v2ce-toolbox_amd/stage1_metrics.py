@@ -8,7 +8,8 @@
 * ``voxel_metrics_batch(pred, gt)``   per-sequence sufficient statistics and values of all of them in one device pass
   (``csrc/voxmetrics.hip`` through ``v2ce_voxmetrics``) and one host synchronisation
 * ``run_stage1_metric(voxels, gt_events, ...)``   the per-recording driver: GT voxelised per pair
-  (``voxelize.gen_discretized_event_volume_batch``), windows of ``seq_len`` pairs scored as one sequence each
+  (``voxelize.gen_discretized_event_volume_batch``), windows of ``seq_len`` pairs scored as one sequence each; with
+  ``losses=...`` also the voxel loss terms of ``losses.calculate_loss`` per window
 
 Values from the statistics: BinaryMatch = (N - FP - FN) / N in f64; BinaryMatchF1 evaluates the reference's f32
 formula (metrics.py:65-90) on the exact counts cast to f32; PoolMSE, MeanRatio and L1 are the f64 sum / count rounded
@@ -246,7 +247,7 @@ class L1(torch.nn.Module):
 def run_stage1_metric(voxels: torch.Tensor, gt_events, gt_counts, frame_timestamps=None, *, seq_len: int = 16,
                       chunk: int = 64, threshold: float = 0.01, pool_sizes: Sequence[int] = (2, 4),
                       pred_events=None, pred_counts=None, height: Optional[int] = None, width: Optional[int] = None,
-                      device=None):
+                      device=None, losses: Optional[Sequence[str]] = None, loss_options: Optional[dict] = None):
     """Score the voxels of P frame pairs against the recording.  ``voxels``: [P, 2, 10, H, W] f32 device tensor (the
     model's output), or None with ``pred_events`` (host structured array grouped by pair), ``pred_counts`` [P],
     ``height`` and ``width``: an event stream voxelised per pair like the GT.
@@ -257,8 +258,18 @@ def run_stage1_metric(voxels: torch.Tensor, gt_events, gt_counts, frame_timestam
 
     Returns ``(summary, records)``: summary[name] = unweighted mean over windows; records = per-window values, the
     pairs of each window, and the pairs whose GT (or predicted events) were empty or had a single timestamp (they
-    score with a zero volume; the reference would raise)."""
+    score with a zero volume; the reference would raise).
+
+    ``losses``: a tuple of loss names of ``losses.calculate_loss`` (``loss_options``: its keyword options).  Each
+    window's ``loss`` and ``loss_dict`` then go into ``records["losses"]`` and their unweighted means over windows
+    into ``records["summary_losses"]``.  A window too small for a requested term (the pyramid needs H, W >= 8) records
+    None for it and for ``loss``."""
     from .voxelize import gen_discretized_event_volume_batch
+    if losses is not None:
+        from . import losses as VL
+        losses = VL.check_loss_names(losses)
+        loss_options = dict(loss_options or {})
+    loss_records: List[dict] = []
     counts = np.asarray(gt_counts, dtype=np.int64).reshape(-1)
     P = counts.size
     if voxels is not None:
@@ -317,6 +328,17 @@ def run_stage1_metric(voxels: torch.Tensor, gt_events, gt_counts, frame_timestam
             for b in range(nb):
                 per_window.append({k: float(v[b]) for k, v in vals.items()})
                 windows.append([c0 + s0 + b * L, c0 + s0 + (b + 1) * L])
+            if losses is not None:
+                small = tuple(n for n in losses if n == "pyramid" and min(10 * L, H, W) < VL.PYRAMID_MIN)
+                fit = tuple(n for n in losses if n not in small)
+                ls = VL.voxel_losses_batch(pvol[sl].reshape(nb, L, 20, H, W), gvol[sl].reshape(nb, L, 20, H, W),
+                                           terms=VL.terms_for(fit))
+                for b in range(nb):
+                    total, d = VL.loss_values([ls.select(b)], fit, **loss_options)
+                    d = {k: float(v) for k, v in d.items()}
+                    if small:
+                        d["pyramid_loss"] = None
+                    loss_records.append({"loss": None if small else float(total), "loss_dict": d})
         del gvol, pvol
     names = list(per_window[0].keys()) if per_window else []
     summary = {k: float(np.mean([w[k] for w in per_window])) for k in names}
@@ -324,11 +346,18 @@ def run_stage1_metric(voxels: torch.Tensor, gt_events, gt_counts, frame_timestam
                "pairs": int(P)}
     if frame_timestamps is not None:
         records["frame_timestamps"] = [int(t) for t in np.asarray(frame_timestamps).reshape(-1)]
+    if losses is not None:
+        mean = lambda vs: float(np.mean([v for v in vs if v is not None])) if any(v is not None for v in vs) else None
+        keys = list(loss_records[0]["loss_dict"]) if loss_records else []
+        records["losses"] = loss_records
+        records["summary_losses"] = {**{k: mean([r["loss_dict"][k] for r in loss_records]) for k in keys},
+                                     "loss": mean([r["loss"] for r in loss_records])}
     return summary, records
 
 
 def write_stage1_results(out_folder: str, summary: Dict[str, float], records) -> None:
-    """stage1_result.csv (metric, mean over windows) and stage1_record.json (per-window values at full precision)."""
+    """stage1_result.csv (metric, mean over windows) and stage1_record.json (per-window values at full precision); with
+    loss terms in the records also stage1_loss_result.csv (term, mean over windows)."""
     import csv
     import json
     import os
@@ -341,3 +370,9 @@ def write_stage1_results(out_folder: str, summary: Dict[str, float], records) ->
             w.writerow([k, repr(float(v))])
     with open(op.join(out_folder, "stage1_record.json"), "w") as f:
         json.dump({"summary": summary, **records}, f, indent=1)
+    if "summary_losses" in records:
+        with open(op.join(out_folder, "stage1_loss_result.csv"), "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(["term", "mean"])
+            for k, v in records["summary_losses"].items():
+                w.writerow([k, "" if v is None else repr(float(v))])

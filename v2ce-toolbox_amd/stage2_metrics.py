@@ -297,6 +297,20 @@ def build_parser():
     p.add_argument("--pred_events", type=str, default=None,
                    help="with --stage1: score this event stream (.npz event_stream or structured .npy), voxelised per "
                         "pair like the GT, instead of the model's voxels; needs --frame_timestamps, skips stage 2")
+    # the stage-1 loss terms (losses.py): opt-in; the defaults of the reference's train/main.py without 'gan'
+    p.add_argument("--stage1_losses", default=None, nargs="*", metavar="NAME",
+                   help="with --stage1: also the reference's voxel loss terms per window (no names: pyramid ef ef_splitp "
+                        "compensation; also pt match norml1 norml2): writes stage1_loss_result.csv and adds \"losses\" "
+                        "to stage1_record.json")
+    p.add_argument("--ef_type", default="c+cl", choices=("only_c", "cl", "c+cl"))
+    p.add_argument("--add_base_loss", action="store_true", help="add the plain MSE to the pyramid loss")
+    p.add_argument("--alpha_pyramid", type=float, default=1000)
+    p.add_argument("--alpha_ef", type=float, default=0.5)
+    p.add_argument("--alpha_efc", type=float, default=5)
+    p.add_argument("--alpha_match", type=float, default=0.5)
+    p.add_argument("--alpha_compensation", type=float, default=1)
+    p.add_argument("--alpha_pt", type=float, default=1)
+    p.add_argument("--alpha_norm", type=float, default=1e-5)
     p.add_argument("-o", "--out_folder", type=str, default="./results")
     p.add_argument("-l", "--log_level", type=str, default="info")
     return p
@@ -380,8 +394,20 @@ def main(argv=None):
     print(op.join(args.out_folder, "abbr_result.csv"))
     if args.stage1:
         from .stage1_metrics import run_stage1_metric
-        s1, r1 = run_stage1_metric(voxels, gt, counts, T, seq_len=args.seq_len)
+        s1, r1 = run_stage1_metric(voxels, gt, counts, T, seq_len=args.seq_len, **_stage1_loss_args(args))
         _report_stage1(args.out_folder, s1, r1)
+
+
+def _stage1_loss_args(args) -> dict:
+    """--stage1_losses and its options as keywords of run_stage1_metric; nothing without the flag."""
+    if args.stage1_losses is None:
+        return {}
+    if not args.stage1:
+        raise SystemExit("--stage1_losses belongs to the stage-1 score: give --stage1")
+    names = tuple(args.stage1_losses) or ("pyramid", "ef", "ef_splitp", "compensation")
+    opts = {k: getattr(args, k) for k in ("ef_type", "add_base_loss", "alpha_pyramid", "alpha_ef", "alpha_efc",
+                                          "alpha_match", "alpha_compensation", "alpha_pt", "alpha_norm")}
+    return {"losses": names, "loss_options": opts}
 
 
 def _report_stage1(out_folder, summary, records):
@@ -390,6 +416,10 @@ def _report_stage1(out_folder, summary, records):
     for k, v in summary.items():
         print(f"{k:22s} {v:.6f}")
     print(op.join(out_folder, "stage1_result.csv"))
+    if "summary_losses" in records:
+        for k, v in records["summary_losses"].items():
+            print(f"{k:22s} {v}")
+        print(op.join(out_folder, "stage1_loss_result.csv"))
 
 
 def _main_pred_events(args):
@@ -407,7 +437,7 @@ def _main_pred_events(args):
     if dev.type == "cuda" and dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
     s1, r1 = run_stage1_metric(None, gt, counts, T, seq_len=args.seq_len, pred_events=pred, pred_counts=pcounts,
-                               height=args.height, width=args.width, device=dev)
+                               height=args.height, width=args.width, device=dev, **_stage1_loss_args(args))
     _report_stage1(args.out_folder, s1, r1)
 
 
