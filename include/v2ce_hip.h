@@ -8,6 +8,14 @@
  * hipStream_t passed as void* (NULL = the null stream); functions only enqueue work and never
  * synchronise; they return V2CE_OK or a negative error code and never throw.
  *
+ * Buffers.  Every array is as large as its entry documents and no larger; a call writes inside the documented sizes only and
+ * reads no output or workspace byte it has not written itself (workspaces and outputs need no initialisation unless an entry
+ * says "zeroed by the caller").  Arrays need the alignment of their element type and nothing more, unless an entry states
+ * otherwise; a stated alignment that is violated is refused with V2CE_ERR_BAD_ARG before anything is launched.  Workspaces
+ * (workspace, tile_ws, fused_ws) are carved into sub-arrays at multiples of 256 bytes: pass them 256-byte aligned.  A call
+ * refused for a workspace that is too small (V2CE_ERR_WORKSPACE) or for an alignment has written nothing
+ * (tests/test_gpu_containment.py holds every entry outside the convolutions to this paragraph).
+ *
  * Activation layout everywhere: [B][T][C][H][W] f32 ("frame-major planar"): the reference's own
  * input layout [B,L,2,H,W] (scripts/v2ce_3d.py:26) and output layout [B,L,20,H,W]
  * (scripts/v2ce_3d.py:29), which is also LDATI's [frames,2,10,H,W] (v2ce.py:351-352).
@@ -144,6 +152,7 @@ int v2ce_ldati_status(const void *workspace, int B, int H, int W, double fps, do
  * previous batch's stats[2]; the same value goes to all three functions), only the bucket scan and the bucket sort remain; otherwise it ignores fused_ws and runs
  * the two-pass path -- same bytes either way (tests/test_gpu_ldati.py::test_fused_count_equals_two_pass).
  * v2ce_ldati_fused_ws_bytes = 0: no fused path for these options ('random', pooled slope) -- use v2ce_ldati_count.
+ * fused_ws must be 16-byte aligned (V2CE_ERR_BAD_ARG otherwise).
  * Dense regime (expected_max_tile_bin_events > 0: the caller's guess of the densest (tile, bin) run, normally the previous
  * batch's stats[1] plus a margin; 0 selects the sparse form above): the dense tile kernel is the count pass and the tile pass
  * at once, every (tile, bin) run in its own slot of that many records (rounded up to 256); v2ce_ldati_emit_fused uses the
@@ -186,7 +195,8 @@ int v2ce_ldati_selfcheck(double fps, int64_t *mismatches /* host [3] */);
 int v2ce_ldati_rank_mode(int32_t *mode);
 
 /* SoA <-> packed 13-byte records {i8 timestamp, i2 x, i2 y, i1 polarity}: the numpy recarray layout
- * of LDATI.py:308-309 (numpy.core.records.fromarrays, itemsize 13).  packed: n*13 bytes. */
+ * of LDATI.py:308-309 (numpy.core.records.fromarrays, itemsize 13).  packed: n*13 bytes, 4-byte aligned (V2CE_ERR_BAD_ARG
+ * otherwise). */
 int v2ce_events_pack(const int64_t *ts, const int16_t *x, const int16_t *y, const int8_t *p,
                      int64_t n, uint8_t *packed, v2ce_stream_t stream);
 int v2ce_events_unpack(const uint8_t *packed, int64_t n, int64_t *ts, int16_t *x, int16_t *y, int8_t *p,
@@ -694,7 +704,7 @@ int v2ce_event_grids_batch(const int64_t *ts, const int16_t *x, const int16_t *y
  *   V2CE_PHYSATT_COUNT_OVERFLOW  a patch holds 2^24 events or more, where the reference's float32 sum is not exact
  * pool_size outside [2, 16], Hp * Wp above 6144 (the finishing kernel's LDS; 260 x 346 fits from pool_size 4 on), H or W
  * above 32767 or n >= 2^31 is V2CE_ERR_UNSUPPORTED, and v2ce_physatt_workspace_bytes returns 0.  A pair without events
- * is valid.
+ * is valid.  The workspace must be 4-byte aligned (V2CE_ERR_BAD_ARG otherwise).
  *
  * v2ce_log_residual_batch: gen_log_frame_residual_batch (:232-247): out f32 [N-1][1][H][W] = lut[f[i+1]] - lut[f[i]],
  * lut the DEVICE float32 [256] table of lin_log(v) (no 1e-6 here).  N >= 2. */

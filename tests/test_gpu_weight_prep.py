@@ -18,14 +18,13 @@ import torch
 from oracle import glue as OG
 from oracle import unet as U
 import weight_ref as R
+from guarded import POISON, Guarded, written
 from v2ce_toolbox_amd import synth
 
 pytestmark = pytest.mark.gpu
 
 OK, BAD_ARG, UNSUPPORTED, WORKSPACE = 0, -1, -2, -4
 NO_PACK, NO_ITERATE = 1, 2
-GUARD = 4096                                     # poisoned bytes in front of every destination; behind it 16x its size more
-POISON = (0xA5, 0x5A)
 SIGMA_BAR = 8 * R.U32                            # f32 trajectory vs f64 trajectory, relative (f32 emulation: <= 2.2 ulps)
 
 
@@ -37,30 +36,6 @@ def L():
 def stream():
     from v2ce_toolbox_amd import hip
     return hip.stream_ptr()
-
-
-class Guarded:
-    """A destination of `n` bytes inside one allocation of GUARD + n + GUARD bytes filled with `poison`."""
-
-    def __init__(self, n, poison):
-        # (the zone behind is large enough to hold what a pack with a wrong kernel volume or layer lookup would write: a
-        # faulty packer shows up as a failed assertion, not as a corrupted neighbour)
-        self.n, self.poison = n, poison
-        self.t = torch.full((GUARD + n + GUARD + 16 * n,), poison, dtype=torch.uint8, device="cuda")
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr() + GUARD
-
-    def body(self):
-        h = self.t.cpu().numpy()
-        assert np.all(h[:GUARD] == self.poison) and np.all(h[GUARD + self.n:] == self.poison), "write outside the destination"
-        return h[GUARD:GUARD + self.n].copy()
-
-
-def written(a, b):
-    """Bytes of two runs on buffers poisoned with POISON[0] / POISON[1]: True where the callee wrote."""
-    return a == b
 
 
 def f32dev(x):

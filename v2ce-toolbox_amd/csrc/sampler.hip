@@ -373,11 +373,14 @@ extern "C" int v2ce_sampler_emit(const float *vox, int B, int H, int W, const v2
     if (const int rc = make_params(vox, B, H, W, options, P)) return rc;
     V2CE_REQUIRE(status, V2CE_ERR_BAD_ARG, "v2ce_sampler_emit: null status");
     hipStream_t st = as_stream(stream);
+    // (every refusal comes before the first write: a refused call leaves status as it was)
+    if (total_events > 0) {
+        V2CE_REQUIRE(ts && x && y && p && workspace, V2CE_ERR_BAD_ARG, "v2ce_sampler_emit: null pointer");
+        V2CE_REQUIRE(workspace_bytes >= v2ce_sampler_workspace_bytes(total_events), V2CE_ERR_WORKSPACE,
+                     "v2ce_sampler_emit: workspace too small");
+    }
     V2CE_HIP_CHECK(hipMemsetAsync(status, 0, sizeof(int32_t), st));
     if (total_events <= 0) return V2CE_OK;
-    V2CE_REQUIRE(ts && x && y && p && workspace, V2CE_ERR_BAD_ARG, "v2ce_sampler_emit: null pointer");
-    V2CE_REQUIRE(workspace_bytes >= v2ce_sampler_workspace_bytes(total_events), V2CE_ERR_WORKSPACE,
-                 "v2ce_sampler_emit: workspace too small");
     char *ws = static_cast<char *>(workspace);
     const size_t kbytes = align256((size_t)total_events * 8);
     P.cursor = reinterpret_cast<unsigned long long *>(ws);
