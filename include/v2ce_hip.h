@@ -14,7 +14,8 @@
  * otherwise; a stated alignment that is violated is refused with V2CE_ERR_BAD_ARG before anything is launched.  Workspaces
  * (workspace, tile_ws, fused_ws) are carved into sub-arrays at multiples of 256 bytes: pass them 256-byte aligned.  A call
  * refused for a workspace that is too small (V2CE_ERR_WORKSPACE) or for an alignment has written nothing
- * (tests/test_gpu_containment.py holds every entry outside the convolutions to this paragraph).
+ * (tests/test_gpu_containment.py holds every entry outside the convolutions to this paragraph,
+ * tests/test_gpu_conv_containment.py the convolutions, on pitched rows).
  *
  * Activation layout everywhere: [B][T][C][H][W] f32 ("frame-major planar"): the reference's own
  * input layout [B,L,2,H,W] (scripts/v2ce_3d.py:26) and output layout [B,L,20,H,W]
@@ -263,6 +264,20 @@ typedef struct {
      * one reference batch be sharded over GPUs sequence by sequence). */
     int32_t absmax_batch_stride;
 } v2ce_conv3d_desc;
+/* Alignment of the device pointers of every v2ce_conv3d_* entry (from the widest access the kernels make; nothing else is
+ * assumed, torch's 512-byte-aligned allocations are not required):
+ *   16 bytes  every tensor in V2CE_LAYOUT_C16 -- x0, x1, tx0, tx1, residual, y, sc_y: the kernels move a quarter of a
+ *             64-byte channel group per lane with 128-bit buffer loads and stores; a row pitch counts whole groups, so ANY
+ *             pitch >= width keeps every group 16-byte aligned -- and every weight buffer: w_packed of both precisions (the
+ *             exact-f32 kernels stage [Cin][k^3][Cout] by 16-byte LDS-DMA pieces), sc_w, tail_w, pred_w, w_up, w_wt, w_table
+ *             (128-bit fragment loads);
+ *    4 bytes  every tensor in V2CE_LAYOUT_PLANAR -- the exact-f32 kernels' x0, x1, residual and y, the planar input of the
+ *             head kernels, pred_y: gathered, staged and stored one float at a time, so any pitch >= width works there too --
+ *             hmap / wmap / thmap / twmap, scale, shift, bias, sc_scale, sc_shift, pred_b, and the range slots
+ *             x0_absmax / x1_absmax / tx0_absmax / tx1_absmax / y_absmax (32-bit loads, 32-bit atomic max).
+ * A pointer of the 16-byte class that is not 16-byte aligned is refused with V2CE_ERR_BAD_ARG before anything is launched.
+ * Padding columns [W, pitch) of a row are never read and never written; of the range slots only [b * s] and [b * s + 1] are
+ * touched, the floats between them belong to the caller (tests/test_gpu_conv_containment.py). */
 #define V2CE_LAYOUT_PLANAR 0
 #define V2CE_LAYOUT_C16 1
 

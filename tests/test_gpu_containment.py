@@ -16,7 +16,8 @@ boundary.  Checked per row:
 
 A workspace 4 bytes short is refused with V2CE_ERR_WORKSPACE and nothing is written.  test_containment_table_covers_the_abi
 (no GPU) requires every export of v2ce_toolbox_amd/hip.py to be exercised by a row, a host-only query, or listed in
-COVERED_ELSEWHERE with the test that guards it."""
+COVERED_ELSEWHERE with the test that guards it (the conv entries: tests/test_gpu_conv_containment.py, the same scheme on
+pitched rows)."""
 import ctypes
 import functools
 
@@ -31,11 +32,11 @@ OK, BAD_ARG, UNSUPPORTED, WORKSPACE = 0, -1, -2, -4
 HOST_ONLY = ("_bytes", "_variant", "_variant_fused", "v2ce_ldati_plan_info", "v2ce_version", "v2ce_last_error",
              "v2ce_ldati_rank_mode", "v2ce_ldati_selfcheck")
 _WP = "tests/test_gpu_weight_prep.py"
-_PITCH = "tests/test_gpu_unet.py::test_conv3d_row_pitch"
+_CONV = "tests/test_gpu_conv_containment.py::test_conv_containment"     # (guarded, poisoned, pitched buffers: its ROWS)
 COVERED_ELSEWHERE = {
-    "v2ce_conv3d_fwd": _PITCH, "v2ce_conv3d_fwd_pred": _PITCH, "v2ce_conv3d_fwd_sc": _PITCH, "v2ce_conv3d_fwd_tail": _PITCH,
-    "v2ce_conv3d_fwd_up2": _PITCH, "v2ce_conv3d_fwd_up2_part": _PITCH, "v2ce_conv3d_fwd_wt": _PITCH,
-    "v2ce_conv3d_fwd_wt_tail": _PITCH, "v2ce_conv3d_head_f16x2": _PITCH,
+    "v2ce_conv3d_fwd": _CONV, "v2ce_conv3d_fwd_pred": _CONV, "v2ce_conv3d_fwd_sc": _CONV, "v2ce_conv3d_fwd_tail": _CONV,
+    "v2ce_conv3d_fwd_up2": _CONV, "v2ce_conv3d_fwd_up2_part": _CONV, "v2ce_conv3d_fwd_wt": _CONV,
+    "v2ce_conv3d_fwd_wt_tail": _CONV, "v2ce_conv3d_head_f16x2": _CONV,
     "v2ce_pack_weights": _WP, "v2ce_pack_weights_f16x2": _WP, "v2ce_pack_weights_f16x2_up": _WP,
     "v2ce_pack_weights_f16x2_wt": _WP, "v2ce_pack_weights_f16x2_wt_slice": _WP, "v2ce_pack_pred_weights_f16x2": _WP,
     "v2ce_pack_head_weights_f16x2": _WP, "v2ce_pack_head_weights_f16x2_c3": _WP, "v2ce_sn_power_iter": _WP,

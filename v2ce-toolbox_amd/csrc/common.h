@@ -36,6 +36,11 @@ inline hipStream_t as_stream(v2ce_stream_t s) { return reinterpret_cast<hipStrea
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+// the alignment include/v2ce_hip.h states for what the conv kernels move in 128-bit pieces (channels-last-16 tensors, weight
+// buffers); null pointers (optional arguments) pass
+template <typename... Ptr>
+inline bool aligned16(Ptr... p) { return ((reinterpret_cast<uintptr_t>(static_cast<const void *>(p)) | ... | (uintptr_t)0) & 15) == 0; }
+
 // power of two s with  amax * s  in [2^14, 2^15): the hi halves use the top of the fp16 range (max
 // 65504) and the lo halves stay normal for every element within 2^-15 of the maximum
 __host__ __device__ __forceinline__ float pow2_prescale(float amax) {

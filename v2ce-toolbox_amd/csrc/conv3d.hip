@@ -1748,6 +1748,10 @@ static int conv3d_dispatch(const v2ce_conv3d_desc *desc, const float *x0, const 
     P.W0p = W0p; P.Winp = Winp; P.Woutp = Woutp;
     P.c16 = d.layout == V2CE_LAYOUT_C16 ? 1 : 0;
     V2CE_REQUIRE(d.layout == V2CE_LAYOUT_PLANAR || d.layout == V2CE_LAYOUT_C16, V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd: layout %d", d.layout);
+    // (the head bridge reads a planar x0 and writes channels-last-16: its inputs need a float's alignment only)
+    V2CE_REQUIRE(g_name_out || (aligned16(w_packed, pred_w, sc_w) &&
+                                (!P.c16 || (aligned16(y, residual, sc_y) && (d.precision != V2CE_PRECISION_F16X2 || aligned16(x0, x1, tx0, tx1))))),
+                 V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd: weight buffers and channels-last-16 tensors must be 16-byte aligned");
     P.act = d.act;
     P.x0_absmax = x0_absmax; P.x1_absmax = d.C1 > 0 ? x1_absmax : nullptr; P.y_absmax = y_absmax;
     P.guard = y_absmax ? y_absmax + 1 : nullptr;

@@ -329,6 +329,7 @@ extern "C" int v2ce_conv3d_head_f16x2(const v2ce_conv3d_desc *desc, const float 
                  d.W0 == d.Win && d.Hout == d.Hin && d.Wout == d.Win && d.layout == V2CE_LAYOUT_C16, V2CE_ERR_UNSUPPORTED,
                  "v2ce_conv3d_head_f16x2: the UNet's head is a 3x3x3 stride-1 conv of 2 or 3 planar input channels into 32 channels-last-16 ones");
     V2CE_REQUIRE(d.act == V2CE_ACT_LEAKY || d.act == V2CE_ACT_RELU || d.act == V2CE_ACT_NONE, V2CE_ERR_BAD_ARG, "v2ce_conv3d_head_f16x2: act %d", d.act);
+    V2CE_REQUIRE(aligned16(w_table, y), V2CE_ERR_BAD_ARG, "v2ce_conv3d_head_f16x2: the weight table and the channels-last-16 output must be 16-byte aligned");
     const int W0p = d.W0_pitch > 0 ? d.W0_pitch : d.W0, Woutp = d.Wout_pitch > 0 ? d.Wout_pitch : d.Wout;
     V2CE_REQUIRE(W0p >= d.W0 && Woutp >= d.Wout, V2CE_ERR_BAD_ARG, "v2ce_conv3d_head_f16x2: a row pitch is smaller than its width");
     V2CE_REQUIRE((long long)d.T * 32 * d.Hout * Woutp < (1ll << 29), V2CE_ERR_UNSUPPORTED,

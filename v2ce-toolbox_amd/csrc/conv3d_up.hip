@@ -1144,6 +1144,8 @@ static int up_dispatch(const v2ce_conv3d_desc *desc, const float *x0, const floa
     V2CE_REQUIRE(d.C0 % 16 == 0 && d.C1 % 16 == 0 && d.Cout % 32 == 0, V2CE_ERR_UNSUPPORTED,
                  "v2ce_conv3d_fwd_up2: channel counts must be multiples of 16 (inputs) / 32 (outputs)");
     V2CE_REQUIRE(d.act >= 0 && d.act <= 2, V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_up2: act %d", d.act);
+    V2CE_REQUIRE(g_name_out || aligned16(x0, x1, w_up, y, sc_w, sc_y), V2CE_ERR_BAD_ARG,
+                 "v2ce_conv3d_fwd_up2: weight buffers and channels-last-16 tensors must be 16-byte aligned");
     const int W0p = d.W0_pitch > 0 ? d.W0_pitch : d.W0, Winp = d.Win_pitch > 0 ? d.Win_pitch : d.Win;
     const int Woutp = d.Wout_pitch > 0 ? d.Wout_pitch : d.Wout;
     V2CE_REQUIRE(W0p >= d.W0 && Winp >= d.Win && Woutp >= d.Wout, V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_up2: a row pitch is smaller than its width");

@@ -1111,6 +1111,8 @@ int wt_dispatch(const v2ce_conv3d_desc *desc, const float *x, const void *w_wt, 
     V2CE_REQUIRE(d.H0 == d.Hin && d.W0 == d.Win && d.Hout == d.Hin && d.Wout == d.Win, V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_wt: input and output planes must have one size");
     V2CE_REQUIRE(d.C0 % 16 == 0 && d.Cout % 64 == 0, V2CE_ERR_UNSUPPORTED, "v2ce_conv3d_fwd_wt: Cin must be a multiple of 16, Cout of 64");
     V2CE_REQUIRE(d.act >= 0 && d.act <= 2, V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_wt: act %d", d.act);
+    V2CE_REQUIRE(g_name_out || (aligned16(x, w_wt, residual, y) && (!tl || aligned16(tl->tx0, tl->tx1, tl->w))), V2CE_ERR_BAD_ARG,
+                 "v2ce_conv3d_fwd_wt: weight buffers and channels-last-16 tensors must be 16-byte aligned");
     const int Winp = d.W0_pitch > 0 ? d.W0_pitch : d.W0, Woutp = d.Wout_pitch > 0 ? d.Wout_pitch : d.Wout;
     V2CE_REQUIRE(Winp >= d.Win && Woutp >= d.Wout, V2CE_ERR_BAD_ARG, "v2ce_conv3d_fwd_wt: a row pitch is smaller than its width");
     V2CE_REQUIRE((long long)d.T * d.C0 * d.Hin * Winp < (1ll << 29) && (long long)d.T * d.Cout * d.Hout * Woutp < (1ll << 29), V2CE_ERR_UNSUPPORTED,
