@@ -44,6 +44,10 @@ EXPORTS = [
     "v2ce_image_grad_workspace_bytes", "v2ce_image_grad_batch", "v2ce_image_units_grad",
 ]
 
+# the training-side entries (include/v2ce_hip_grad.h), bound next to the others
+GRAD_EXPORTS = ("v2ce_voxloss_grads_workspace_bytes", "v2ce_voxloss_grads", "v2ce_volume_loss_grads_workspace_bytes",
+                "v2ce_volume_loss_grads")
+
 
 LAYOUT_PLANAR, LAYOUT_C16 = 0, 1
 
@@ -106,6 +110,14 @@ class VoxLossesStats(ctypes.Structure):
                 ("ef_n", ctypes.c_int64 * 4), ("ef_sq_sum", ctypes.c_double * 4), ("comp_n", ctypes.c_int64),
                 ("comp_sq_sum", ctypes.c_double), ("match_n", ctypes.c_int64), ("match_sum", ctypes.c_double),
                 ("match_low", ctypes.c_int64)]
+
+
+class VoxLossGradCoeffs(ctypes.Structure):
+    """``v2ce_voxloss_grad_coeffs`` (include/v2ce_hip_grad.h): one f64 factor per linear piece of the loss gradient."""
+    _fields_ = [("struct_size", ctypes.c_int64), ("a_sq", ctypes.c_double), ("a_pyr", ctypes.c_double * 3),
+                ("a_t3", ctypes.c_double), ("a_t5", ctypes.c_double), ("a_ef", ctypes.c_double * 4),
+                ("a_comp", ctypes.c_double), ("a_match", ctypes.c_double), ("a_l1", ctypes.c_double),
+                ("a_l2", ctypes.c_double)]
 
 
 VOXELIZE_EMPTY, VOXELIZE_SINGLE_TIMESTAMP, VOXELIZE_BAD_XY, VOXELIZE_BAD_RANGE = 1, 2, 4, 8
@@ -268,6 +280,15 @@ def lib() -> ctypes.CDLL:
     L.v2ce_volume_losses_workspace_bytes.restype = sz
     L.v2ce_volume_losses.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]
     L.v2ce_volume_losses.restype = ctypes.c_int
+    cp = ctypes.POINTER(VoxLossGradCoeffs)
+    L.v2ce_voxloss_grads_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, cp, sz]
+    L.v2ce_voxloss_grads_workspace_bytes.restype = sz
+    L.v2ce_voxloss_grads.argtypes = [vp, vp, i32, i32, i32, i32, i32, cp, sz, vp, vp, vp, sz, vp]
+    L.v2ce_voxloss_grads.restype = ctypes.c_int
+    L.v2ce_volume_loss_grads_workspace_bytes.argtypes = [i32, i32, i32, i32, cp, sz]
+    L.v2ce_volume_loss_grads_workspace_bytes.restype = sz
+    L.v2ce_volume_loss_grads.argtypes = [vp, vp, i32, i32, i32, i32, cp, sz, vp, vp, vp, sz, vp]
+    L.v2ce_volume_loss_grads.restype = ctypes.c_int
     L.v2ce_voxelize_batch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
     L.v2ce_voxelize_batch_workspace_bytes.restype = sz
     L.v2ce_voxelize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]

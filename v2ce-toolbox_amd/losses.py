@@ -9,17 +9,28 @@ pass over ``pred`` and ``gt``:
 * drop-ins ``Pyramid3dLoss(add_base_loss)``, ``PyramidTemporalLoss()`` on ``[N, D, H, W]`` and ``CompensationLoss()``,
   ``MatchLoss()`` on ``[B, L, 20, H, W]``: the reference's constructor arguments and ``forward``, 0-d f32 device tensors
 * ``calculate_loss(pred_voxels, gt_voxels, loss=...)``   the reference's weighted total and ``loss_dict``
+* ``voxel_loss_grads_batch(pred, gt, loss=..., ...)`` / ``volume_loss_grads_batch``   the gradient of that total with
+  respect to ``pred`` (``csrc/voxlossgrads.hip`` through ``v2ce_voxloss_grads`` / ``v2ce_volume_loss_grads``), f32, shaped
+  like ``pred``; ``grad_coeffs`` turns a loss list, its options and the shape into the kernel's f64 factors
 
 Every value is the f64 quotient of the f64 statistics, rounded to f32 once; the reference computes in f32 throughout
-(its ``torch.norm`` is off by up to 5e-4 relative at full size).  There are no gradients and there is no CPU path.
+(its ``torch.norm`` is off by up to 5e-4 relative at full size).  Every gradient element is the f64 closed form of the
+reference's autograd result, rounded to f32 once.  When a prediction requires grad, ``calculate_loss`` and the drop-in
+modules return a value with a ``grad_fn`` (one ``torch.autograd.Function`` per refinement stage: the statistics call
+forward, one gradient call backward, no host synchronisation in the backward); otherwise, and under
+``torch.no_grad()``, they do exactly the statistics call.  ``gt`` gets no gradient and there is no double backward.
+The match gradient is the f64 softmax, so it stays finite where the reference's f32 ``log(softmax)`` has underflowed
+(``match_low > 0``).  There is no CPU path.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Dict, Optional, Sequence
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import hip
 
@@ -247,6 +258,9 @@ class Pyramid3dLoss(torch.nn.Module):
         self.add_base_loss = add_base_loss
 
     def forward(self, pred, target):
+        if _wants_grad(pred):
+            return _StageLoss.apply(pred, target, _Stage(("pyramid",), dict(add_base_loss=self.add_base_loss,
+                                                                            alpha_pyramid=1), volume=True))
         s = volume_losses_batch(pred, target, terms=("pyramid",)).total()
         return _scalar(s.pyramid(self.add_base_loss)[0], pred.device)
 
@@ -255,6 +269,8 @@ class PyramidTemporalLoss(torch.nn.Module):
     """losses.py PyramidTemporalLoss on [N, D, H, W]: MSE plus the MSE of two average pools along D, / 2."""
 
     def forward(self, pred, target):
+        if _wants_grad(pred):
+            return _StageLoss.apply(pred, target, _Stage(("pt",), dict(alpha_pyramid=1), volume=True))
         s = volume_losses_batch(pred, target, terms=("temporal",)).total()
         return _scalar(s.pt()[0], pred.device)
 
@@ -263,6 +279,8 @@ class CompensationLoss(torch.nn.Module):
     """losses.py CompensationLoss on [B, L, 20, H, W]: its dim = (2, 3) reduces channels and rows."""
 
     def forward(self, pred, target):
+        if _wants_grad(pred):
+            return _StageLoss.apply(pred, target, _Stage(("compensation",), dict(alpha_compensation=1)))
         s = voxel_losses_batch(pred, target, terms=("compensation",)).total()
         return _scalar(s.compensation()[0], pred.device)
 
@@ -271,6 +289,8 @@ class MatchLoss(torch.nn.Module):
     """losses.py MatchLoss on [B, L, 20, H, W]: NLL of softmax over l at the first argmax over l of the target."""
 
     def forward(self, pred, target):
+        if _wants_grad(pred):
+            return _StageLoss.apply(pred, target, _Stage(("match",), dict(alpha_match=1)))
         s = voxel_losses_batch(pred, target, terms=("match",)).total()
         return _scalar(s.match()[0], pred.device)
 
@@ -354,8 +374,239 @@ def calculate_loss(pred_voxels, gt_voxels, *, loss=("pyramid", "ef", "ef_splitp"
     if not stages:
         raise ValueError("pred_voxels is an empty list")
     terms = terms_for(loss)
-    stats = [voxel_losses_batch(p, gt_voxels, terms=terms).total() for p in stages]
-    total, d = loss_values(stats, loss, ef_type=ef_type, add_base_loss=add_base_loss, alpha_pyramid=alpha_pyramid,
+    opts = dict(ef_type=ef_type, add_base_loss=add_base_loss, alpha_pyramid=alpha_pyramid, alpha_ef=alpha_ef,
+                alpha_efc=alpha_efc, alpha_match=alpha_match, alpha_compensation=alpha_compensation, alpha_pt=alpha_pt,
+                alpha_norm=alpha_norm)
+    if not any(_wants_grad(p) for p in stages):
+        stats = [voxel_losses_batch(p, gt_voxels, terms=terms).total() for p in stages]
+        total, d = loss_values(stats, loss, **opts)
+        return _scalar(total, gt_voxels.device), {k: torch.tensor(float(v), dtype=torch.float32) for k, v in d.items()}
+    # one autograd node per stage: its value is the stage's share of the total, its backward one gradient call
+    plans = [_Stage(loss, opts, stages=len(stages)) for _ in stages]
+    shares = [_StageLoss.apply(p, gt_voxels, plan) for p, plan in zip(stages, plans)]
+    total, d = loss_values([plan.stats.total() for plan in plans], loss, **opts)
+    if len(shares) == 1:
+        out = shares[0]                                   # its value is the total itself
+    else:
+        # the total as the no-grad call rounds it (f64 over all stages, one rounding), carried by the stages' nodes:
+        # the bracket is exactly zero and passes the incoming gradient to every stage unchanged
+        s = torch.stack(shares).sum()
+        out = _scalar(total, gt_voxels.device) + (s - s.detach())
+    return out, {k: torch.tensor(float(v), dtype=torch.float32) for k, v in d.items()}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# gradients
+
+_OPTION_DEFAULTS = dict(ef_type="c+cl", add_base_loss=False, alpha_pyramid=1000, alpha_ef=0.5, alpha_efc=5,
+                        alpha_match=0.5, alpha_compensation=1, alpha_pt=1, alpha_norm=1e-5)
+DEFAULT_LOSS = ("pyramid", "ef", "ef_splitp", "compensation")
+VOLUME_LOSS_NAMES = ("pyramid", "pt")
+COEFF_FIELDS = tuple(n for n, _ in hip.VoxLossGradCoeffs._fields_ if n != "struct_size")
+
+
+def _wants_grad(t) -> bool:
+    return torch.is_grad_enabled() and isinstance(t, torch.Tensor) and t.requires_grad
+
+
+def grad_coeffs(shape, loss=DEFAULT_LOSS, *, ef_type="c+cl", add_base_loss=False, alpha_pyramid=1000, alpha_ef=0.5,
+                alpha_efc=5, alpha_match=0.5, alpha_compensation=1, alpha_pt=1, alpha_norm=1e-5, stages=1,
+                pred_sq_sum=None) -> hip.VoxLossGradCoeffs:
+    """The factors of ``v2ce_voxloss_grad_coeffs`` for the gradient of ``calculate_loss(..., loss=loss, <options>)`` on a
+    ``shape`` [B, L, 20, H, W] prediction (or [N, D, H, W]: 'pyramid' and 'pt' only): per linear piece of the loss its
+    alpha, 2 / (the batch-total count of the forward record), 1 / k^3, the / 3 and / 2 of the pyramid and temporal
+    classes, / len(kinds) of the event-frame term and 1 / ``stages`` in one f64.  ``pred_sq_sum``: the batch total of
+    the forward record's field, needed by 'norml2' (whose gradient is zero where the norm is).  As in ``loss_values``,
+    ``alpha_pt`` is accepted and not used."""
+    loss = check_loss_names(loss)
+    if ef_type not in EF_TYPES:
+        raise ValueError(f"Invalid ef_type {ef_type}!")
+    if int(stages) < 1:
+        raise ValueError(f"stages must be >= 1, got {stages}")
+    shape = tuple(int(v) for v in shape)
+    if len(shape) == 5:
+        B, L, C, H, W = shape
+        if C != CHANNELS:
+            raise ValueError(f"shape must be [b, l, 20, h, w], got {shape}")
+        N, D = 2 * B, 10 * L
+    elif len(shape) == 4:
+        N, D, H, W = shape
+        B = L = 0
+        bad = [n for n in loss if n in LOSS_NAMES and n not in VOLUME_LOSS_NAMES]
+        if bad:
+            raise ValueError(f"[n, d, h, w] volumes have the losses {VOLUME_LOSS_NAMES} only, got {bad}")
+    else:
+        raise ValueError(f"shape must be [b, l, 20, h, w] or [n, d, h, w], got {shape}")
+    _check_sizes(terms_for(loss), D, H, W)
+    c = hip.VoxLossGradCoeffs(struct_size=ctypes.sizeof(hip.VoxLossGradCoeffs))
+    s = 1.0 / int(stages)
+    HW = H * W
+    n = N * D * HW
+    a_sq = 0.0
+    if "pyramid" in loss:
+        for q, k in enumerate((2, 4, 8)):
+            c.a_pyr[q] = alpha_pyramid * 2.0 / (3.0 * k ** 3 * (N * (D // k) * (H // k) * (W // k))) * s
+        if add_base_loss:
+            a_sq += alpha_pyramid * 2.0 / (3.0 * n) * s
+    if "pt" in loss:
+        c.a_t3 = alpha_pyramid * 2.0 / (2.0 * 3.0 * (N * HW * ((D - 1) // 3 + 1))) * s
+        c.a_t5 = alpha_pyramid * 2.0 / (2.0 * 5.0 * (N * HW * (D // 5))) * s
+        a_sq += alpha_pyramid * 2.0 / (2.0 * n) * s
+    c.a_sq = a_sq
+    kinds = tuple(k for k in ("ef", "ef_splitp") if k in loss)
+    if kinds:
+        w_c = {"only_c": 1.0, "cl": 0.0, "c+cl": float(alpha_efc)}[ef_type]
+        w_cl = {"only_c": 0.0, "cl": 1.0, "c+cl": 1.0}[ef_type]
+        base = alpha_ef / len(kinds) * s
+        ef_n = (B * L * HW, B * HW, B * L * 2 * HW, B * 2 * HW)
+        if "ef" in kinds:
+            c.a_ef[0] = base * w_c * 2.0 / ef_n[0]
+            c.a_ef[1] = base * w_cl * 2.0 / ef_n[1]
+        if "ef_splitp" in kinds:
+            c.a_ef[2] = base * 2.0 * w_c * 2.0 / ef_n[2]
+            c.a_ef[3] = base * 2.0 * w_cl * 2.0 / ef_n[3]
+    if "compensation" in loss:
+        c.a_comp = alpha_compensation * 2.0 / (B * L * W) * s
+    if "match" in loss:
+        c.a_match = alpha_match * 1.0 / (B * CHANNELS * HW) * s
+    if "norml1" in loss:
+        c.a_l1 = alpha_norm * s
+    if "norml2" in loss:
+        if pred_sq_sum is None:
+            raise ValueError("'norml2' needs pred_sq_sum, the batch total of the forward statistics")
+        norm = math.sqrt(float(pred_sq_sum))
+        c.a_l2 = alpha_norm / norm * s if norm > 0 else 0.0
+    return c
+
+
+def _check_f32_device(t, name, device):
+    """ValueError for what a gradient call refuses in an argument of its own."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise ValueError(f"{name} must be a float32 tensor (got {getattr(t, 'dtype', type(t))})")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if t.device != device:
+        raise ValueError(f"{name} lives on {t.device}, pred on {device}")
+
+
+def _overlaps(a, b) -> bool:
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * 4 and b0 < a0 + a.numel() * 4
+
+
+_WHAT = {5: "[b, l, 20, h, w] (channels (p c): 2 polarities x 10 bins)", 4: "[n, d, h, w]"}
+
+
+def _check_grad_pair(pred, gt, ndim):
+    for t, nm in ((pred, "pred"), (gt, "gt")):
+        if isinstance(t, torch.Tensor) and t.dtype != torch.float32:
+            raise ValueError(f"{nm} must be float32 (got {t.dtype})")
+    _check_pair(pred, gt, ndim, _WHAT[ndim])
+    return tuple(int(v) for v in pred.shape)
+
+
+def _run_grads(entry, pred, gt, dims, coef, upstream, grad):
+    dev = pred.device
+    if grad is not None:
+        _check_f32_device(grad, "grad", dev)
+        if grad.shape != pred.shape:
+            raise ValueError(f"grad {tuple(grad.shape)} and pred {tuple(pred.shape)} differ in shape")
+        if _overlaps(grad, pred) or _overlaps(grad, gt):
+            raise ValueError("grad overlaps pred or gt")
+    if upstream is not None:
+        _check_f32_device(upstream, "upstream", dev)
+        if upstream.numel() != 1:
+            raise ValueError(f"upstream must hold one element, got {tuple(upstream.shape)}")
+        if _overlaps(upstream, pred) or _overlaps(upstream, gt) or (grad is not None and _overlaps(upstream, grad)):
+            raise ValueError("upstream overlaps pred, gt or grad")
+    L = hip.lib()
+    size = ctypes.sizeof(hip.VoxLossGradCoeffs)
+    ws_bytes = getattr(L, entry + "_workspace_bytes")(*dims, ctypes.byref(coef), size)
+    if ws_bytes == 0:
+        raise hip.V2ceHipError(f"{entry}: unsupported shape {tuple(pred.shape)} for these coefficients")
+    with torch.cuda.device(dev):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        if grad is None:
+            grad = torch.empty_like(pred)
+        hip.check(getattr(L, entry)(pred.data_ptr(), gt.data_ptr(), *dims, ctypes.byref(coef), size, hip.ptr(upstream),
+                                    grad.data_ptr(), ws.data_ptr(), ws_bytes, hip.stream_ptr(dev)), entry)
+    return grad
+
+
+def voxel_loss_grads_batch(pred: torch.Tensor, gt: torch.Tensor, *, loss: Sequence[str] = DEFAULT_LOSS, ef_type="c+cl",
+                           add_base_loss=False, alpha_pyramid=1000, alpha_ef=0.5, alpha_efc=5, alpha_match=0.5,
+                           alpha_compensation=1, alpha_pt=1, alpha_norm=1e-5, stages=1,
+                           upstream: Optional[torch.Tensor] = None, stats: Optional[VoxLosses] = None,
+                           grad: Optional[torch.Tensor] = None, coef: Optional[hip.VoxLossGradCoeffs] = None) -> torch.Tensor:
+    """d calculate_loss(pred, gt, loss=loss, <options>)[0] / d pred for ``pred``, ``gt`` [B, L, 20, H, W] (f32, contiguous,
+    one device): an f32 tensor shaped like ``pred``, every element written.  ``stages``: the number of refinement stages
+    the total averages over (this call is one of them).  ``upstream``: one f32 on the device that multiplies the
+    gradient (an incoming ``grad_output``); nothing is copied to the host.  ``stats``: the forward statistics of this
+    pair, if at hand -- only 'norml2' needs them, and they are computed here (one synchronisation) when it does and
+    they were not passed.  ``grad``: write here instead of allocating; it must not overlap ``pred`` or ``gt``.
+    ``coef``: the factors themselves, instead of ``loss`` and its options (``grad_coeffs``)."""
+    dims = _check_grad_pair(pred, gt, 5)
+    if coef is None:
+        loss = check_loss_names(loss)
+        sq = None
+        if "norml2" in loss:
+            if stats is None:
+                stats = voxel_losses_batch(pred, gt, terms=())
+            sq = float(np.sum(stats.pred_sq_sum))
+        coef = grad_coeffs(dims, loss, ef_type=ef_type, add_base_loss=add_base_loss, alpha_pyramid=alpha_pyramid,
                            alpha_ef=alpha_ef, alpha_efc=alpha_efc, alpha_match=alpha_match,
-                           alpha_compensation=alpha_compensation, alpha_pt=alpha_pt, alpha_norm=alpha_norm)
-    return _scalar(total, gt_voxels.device), {k: torch.tensor(float(v), dtype=torch.float32) for k, v in d.items()}
+                           alpha_compensation=alpha_compensation, alpha_pt=alpha_pt, alpha_norm=alpha_norm, stages=stages,
+                           pred_sq_sum=sq)
+    return _run_grads("v2ce_voxloss_grads", pred, gt, dims, coef, upstream, grad)
+
+
+def volume_loss_grads_batch(pred: torch.Tensor, gt: torch.Tensor, *, loss: Sequence[str] = VOLUME_LOSS_NAMES,
+                            add_base_loss=False, alpha_pyramid=1000, stages=1, upstream: Optional[torch.Tensor] = None,
+                            grad: Optional[torch.Tensor] = None,
+                            coef: Optional[hip.VoxLossGradCoeffs] = None) -> torch.Tensor:
+    """The [N, D, H, W] counterpart of ``voxel_loss_grads_batch``: the 'pyramid' and 'pt' terms of the volumes that
+    'b l (p c) h w -> (b p) (l c) h w' makes, weighted as ``calculate_loss`` weights them."""
+    dims = _check_grad_pair(pred, gt, 4)
+    if coef is None:
+        coef = grad_coeffs(dims, loss, add_base_loss=add_base_loss, alpha_pyramid=alpha_pyramid, stages=stages)
+    return _run_grads("v2ce_volume_loss_grads", pred, gt, dims, coef, upstream, grad)
+
+
+class _Stage:
+    """What one refinement stage's autograd node computes: the loss list and options of its share of the total, and
+    after the forward its statistics (per row)."""
+
+    def __init__(self, loss, opts, stages=1, volume=False):
+        self.loss, self.opts, self.stages, self.volume = tuple(loss), {**_OPTION_DEFAULTS, **opts}, stages, volume
+        self.stats = None
+
+
+class _StageLoss(torch.autograd.Function):
+    """forward: the statistics call of today and this stage's share of the weighted total (its terms / stages) as a
+    0-d f32 device tensor; backward: one gradient call that reads grad_output on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, plan):
+        terms = terms_for(plan.loss)
+        plan.stats = (volume_losses_batch if plan.volume else voxel_losses_batch)(pred, gt, terms=terms)
+        total, _ = loss_values([plan.stats.total()], plan.loss, **plan.opts)
+        ctx.save_for_backward(pred, gt)
+        ctx.plan = plan
+        ctx.set_materialize_grads(False)
+        return _scalar(np.float32(np.float64(total) / plan.stages) if plan.stages != 1 else total, pred.device)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        if grad_output is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        pred, gt = ctx.saved_tensors
+        plan = ctx.plan
+        up = grad_output.detach().to(device=pred.device, dtype=torch.float32).reshape(1).contiguous()
+        o = plan.opts
+        if plan.volume:
+            g = volume_loss_grads_batch(pred, gt, loss=plan.loss, add_base_loss=o["add_base_loss"],
+                                        alpha_pyramid=o["alpha_pyramid"], stages=plan.stages, upstream=up)
+        else:
+            g = voxel_loss_grads_batch(pred, gt, loss=plan.loss, stages=plan.stages, upstream=up, stats=plan.stats, **o)
+        return g, None, None
