@@ -1,0 +1,208 @@
+"""Fit the prediction head to a recording: the smallest training workflow of the reference (everything frozen but
+``UNet.pred`` in train/main.py), entirely on the package's own kernels.
+
+    history = fit_head(model, image_units, gt_voxels, steps=200, lr=1e-3)
+
+The trunk is frozen, so its output -- the 32-channel features in front of ``UNet.pred`` -- is computed once per window
+(``V2ce3d.forward_features``) and every step is ``PredHead`` -> ``losses.calculate_loss`` -> ``backward()`` -> one
+``torch.optim`` step on the head's 660 parameters.  ``v2ce_finetune.py`` is the command line (``main`` below).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import logging
+import os
+import os.path as op
+from typing import List, Sequence
+
+import numpy as np
+import torch
+
+from . import losses
+from .pred_head import PredHead
+
+logger = logging.getLogger("V2CE")
+DEFAULT_CACHE_BYTES = 8 << 30
+
+
+def _windows(image_units, gt_voxels):
+    """-> [(x [B, L, 2, H, W], gt [B, L, 20, H, W])]: the model calls of one pass over the data."""
+    xs = list(image_units) if isinstance(image_units, (list, tuple)) else [image_units]
+    gs = list(gt_voxels) if isinstance(gt_voxels, (list, tuple)) else [gt_voxels]
+    if len(xs) != len(gs) or not xs:
+        raise ValueError(f"{len(xs)} image-unit windows for {len(gs)} ground-truth windows")
+    for x, g in zip(xs, gs):
+        if not (isinstance(x, torch.Tensor) and isinstance(g, torch.Tensor)) or x.dim() != 5 or g.dim() != 5:
+            raise ValueError("every window is a pair of tensors [b, l, 2, h, w] and [b, l, 20, h, w]")
+        if (x.shape[0], x.shape[1], x.shape[3], x.shape[4]) != (g.shape[0], g.shape[1], g.shape[3], g.shape[4]):
+            raise ValueError(f"image units {tuple(x.shape)} and ground truth {tuple(g.shape)} differ in b, l, h or w")
+    return list(zip(xs, gs))
+
+
+def fit_head(model, image_units, gt_voxels, *, loss: Sequence[str] = losses.DEFAULT_LOSS, steps: int, lr: float,
+             optimizer: str = "adam", cache_bytes: int = DEFAULT_CACHE_BYTES, **loss_options) -> List[dict]:
+    """Fit ``model.UNet.pred`` to ground-truth voxels with the rest of the network frozen.
+
+    ``image_units`` [B, L, 2, H, W] with ``gt_voxels`` [B, L, 20, H, W] (f32, on the model's device), or lists of such
+    windows; step k works on window k % len(windows).  ``loss`` and ``loss_options`` are those of
+    ``losses.calculate_loss``; ``optimizer`` is 'adam' or 'sgd' (plain, no momentum) at learning rate ``lr``.
+
+    The features of a window are computed once and kept while the kept ones fit in ``cache_bytes``; a window beyond the
+    budget is recomputed at each of its steps.  Every feature pass starts from the spectral-norm state the model had on
+    entry, so a window's features do not depend on whether they were cached.
+
+    Returns the history: per step ``{"loss": float, "loss_dict": {name: float}}``, the values before that step's
+    update.  On return the model differs from its state on entry in ``UNet.pred.conv3d.weight`` and ``.bias`` only:
+    the spectral-norm u / v and the call counter are restored."""
+    loss = losses.check_loss_names(loss)
+    if optimizer not in ("adam", "sgd"):
+        raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
+    if int(steps) < 0:
+        raise ValueError(f"steps must be >= 0, got {steps}")
+    windows = _windows(image_units, gt_voxels)
+    head = PredHead.from_model(model)
+    opt = (torch.optim.Adam if optimizer == "adam" else torch.optim.SGD)(head.parameters(), lr=lr)
+    snap = model.sn_snapshot()
+    cache, used = {}, 0
+
+    def features(i):
+        nonlocal used
+        if i in cache:
+            return cache[i]
+        model.sn_restore(snap)
+        f = model.forward_features(windows[i][0])
+        nb = f.numel() * 4
+        if used + nb <= cache_bytes:
+            cache[i], used = f, used + nb
+        return f
+
+    history = []
+    try:
+        for k in range(int(steps)):
+            i = k % len(windows)
+            opt.zero_grad(set_to_none=True)
+            pred = head(features(i))
+            total, d = losses.calculate_loss(pred, windows[i][1].contiguous(), loss=loss, **loss_options)
+            total.backward()
+            opt.step()
+            history.append({"loss": float(total.detach()), "loss_dict": {n: float(v) for n, v in d.items()}})
+    finally:
+        model.sn_restore(snap)
+    head.write_back(model)
+    return history
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# command line
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Fit the prediction head of a V2CE checkpoint to a recording")
+    p.add_argument("-f", "--image_folder", type=str, help="The folder containing the images")
+    p.add_argument("--npy_frames", type=str, help="uint8 [N,H,W] grayscale frames in a .npy file")
+    p.add_argument("--synthetic", type=int, default=0, help="generate N synthetic frames instead of reading")
+    p.add_argument("--synthetic_weights", type=int, default=None, help="seed of synthetic weights")
+    p.add_argument("-m", "--model_path", type=str, default="./weights/v2ce_3d.pt")
+    p.add_argument("--precision", type=str, default="f16x2", choices=["f16x2", "f32"])
+    p.add_argument("--seq_len", type=int, default=16)
+    p.add_argument("--width", type=int, default=346)
+    p.add_argument("--height", type=int, default=260)
+    p.add_argument("--max_frame_num", type=int, default=1800)
+    p.add_argument("--device", type=str, default="cuda")
+    p.add_argument("--gt_events", type=str, required=True,
+                   help="GT events: .npz with 'event_stream' or a structured .npy (timestamp, x, y, polarity)")
+    p.add_argument("--frame_timestamps", type=str, help="int64 us frame times [N] (.npy)")
+    p.add_argument("--fps", type=float, default=30, help="without --frame_timestamps: T_i = int(i * 1 / fps * 1e6)")
+    p.add_argument("--stage1_losses", "--losses", dest="losses", default=None, nargs="*", metavar="NAME",
+                   help="the voxel loss terms (default: pyramid ef ef_splitp compensation; also pt match norml1 norml2)")
+    p.add_argument("--ef_type", default="c+cl", choices=("only_c", "cl", "c+cl"))
+    p.add_argument("--add_base_loss", action="store_true", help="add the plain MSE to the pyramid loss")
+    p.add_argument("--alpha_pyramid", type=float, default=1000)
+    p.add_argument("--alpha_ef", type=float, default=0.5)
+    p.add_argument("--alpha_efc", type=float, default=5)
+    p.add_argument("--alpha_match", type=float, default=0.5)
+    p.add_argument("--alpha_compensation", type=float, default=1)
+    p.add_argument("--alpha_pt", type=float, default=1)
+    p.add_argument("--alpha_norm", type=float, default=1e-5)
+    p.add_argument("--steps", type=int, default=100)
+    p.add_argument("--lr", type=float, default=1e-3)
+    p.add_argument("--optimizer", default="adam", choices=("adam", "sgd"))
+    p.add_argument("--cache_gb", type=float, default=DEFAULT_CACHE_BYTES / 2 ** 30, help="feature cache budget")
+    p.add_argument("-o", "--out", type=str, default="./tuned.pt", help="the tuned state_dict (v2ce.py -m loads it)")
+    p.add_argument("--history", type=str, default=None, help="the per-step history as JSON (default: <out>.history.json)")
+    p.add_argument("-l", "--log_level", type=str, default="info")
+    return p
+
+
+def recording_windows(frames, gt_events, T, *, seq_len, width, height, device):
+    """Frames [N, H, W] uint8, GT events and frame times [N] -> (image-unit windows, GT voxel windows): consecutive
+    windows of ``seq_len`` pairs (the last may be shorter), the image units centre-cropped on the width as
+    glue.infer_center_image_unit crops them, the GT of each pair voxelised over its own time range as
+    stage1_metrics.run_stage1_metric builds it."""
+    from . import glue
+    from .stage2_metrics import split_by_frames
+    from .voxelize import gen_discretized_event_volume_batch
+    units = torch.from_numpy(glue.image_pre_processing(np.asarray(frames), height=height))
+    fw = units.shape[-1]
+    units = units[..., fw // 2 - width // 2: fw // 2 + width // 2].contiguous()
+    P, H, W = int(units.shape[0]), int(units.shape[2]), int(units.shape[3])
+    gt, counts, dropped = split_by_frames(gt_events, np.asarray(T, dtype=np.int64)[:P + 1])
+    logger.info(f"{len(gt)} GT events in {P} pairs; {dropped} outside the frames' time range dropped")
+    goff = np.concatenate([[0], np.cumsum(counts)])
+    xs, gs = [], []
+    for c0 in range(0, P, seq_len):
+        c1 = min(P, c0 + seq_len)
+        gvol, _ = gen_discretized_event_volume_batch(gt[goff[c0]:goff[c1]], counts[c0:c1], 10, H, W, device=device)
+        xs.append(units[c0:c1][None].to(device))
+        gs.append(gvol.reshape(1, c1 - c0, 20, H, W).contiguous())
+    return xs, gs
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    logging.basicConfig(level=getattr(logging, args.log_level.upper()))
+    from . import glue, synth
+    from .stage2_metrics import load_events
+    from .v2ce import get_trained_mode, read_image_folder
+    from .v2ce_3d import V2ce3d
+    if str(args.device).startswith("cuda") and torch.device(args.device).index is not None:
+        torch.cuda.set_device(torch.device(args.device))
+    sources = [args.image_folder, args.npy_frames, args.synthetic or None]
+    assert sum(s is not None for s in sources) == 1, "specify exactly one frame source"
+    if args.image_folder is not None:
+        frames = read_image_folder(args.image_folder, args.max_frame_num)
+    elif args.npy_frames is not None:
+        frames = np.load(args.npy_frames)[:args.max_frame_num]
+    else:
+        frames = synth.synthetic_frames(args.synthetic, args.height, args.width)
+    if args.synthetic_weights is not None:
+        model = V2ce3d(precision=args.precision)
+        model.load_state_dict(synth.make_state_dict(args.synthetic_weights))
+        model = model.eval().to(args.device)
+    else:
+        model = get_trained_mode(args.model_path, args.device, args.precision)
+    n = len(frames)
+    if args.frame_timestamps is not None:
+        T = np.load(args.frame_timestamps).astype(np.int64).reshape(-1)
+        if T.size < n:
+            raise ValueError(f"{args.frame_timestamps}: {T.size} frame times for {n} frames")
+        T = T[:n]
+    else:
+        T = np.array([glue.frame_offset_us(i, args.fps) for i in range(n)], dtype=np.int64)
+    xs, gs = recording_windows(frames, load_events(args.gt_events), T, seq_len=args.seq_len, width=args.width,
+                               height=args.height, device=args.device)
+    names = tuple(args.losses) if args.losses else losses.DEFAULT_LOSS
+    opts = {k: getattr(args, k) for k in ("ef_type", "add_base_loss", "alpha_pyramid", "alpha_ef", "alpha_efc",
+                                          "alpha_match", "alpha_compensation", "alpha_pt", "alpha_norm")}
+    history = fit_head(model, xs, gs, loss=names, steps=args.steps, lr=args.lr, optimizer=args.optimizer,
+                       cache_bytes=int(args.cache_gb * 2 ** 30), **opts)
+    os.makedirs(op.dirname(op.abspath(args.out)), exist_ok=True)
+    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, args.out)
+    hist_path = args.history or args.out + ".history.json"
+    with open(hist_path, "w") as f:
+        json.dump({"loss": list(names), "options": opts, "steps": args.steps, "lr": args.lr, "optimizer": args.optimizer,
+                   "windows": len(xs), "history": history}, f, indent=1)
+    if history:
+        logger.info(f"loss {history[0]['loss']:.6g} -> {history[-1]['loss']:.6g} over {len(history)} steps")
+    print(args.out)
+    print(hist_path)

@@ -48,6 +48,10 @@ EXPORTS = [
 GRAD_EXPORTS = ("v2ce_voxloss_grads_workspace_bytes", "v2ce_voxloss_grads", "v2ce_volume_loss_grads_workspace_bytes",
                 "v2ce_volume_loss_grads")
 
+# the trainable layers (include/v2ce_hip_train.h): forward and backward of the prediction head
+TRAIN_EXPORTS = ("v2ce_pred_head_fwd_workspace_bytes", "v2ce_pred_head_fwd", "v2ce_pred_head_grads_workspace_bytes",
+                 "v2ce_pred_head_grads")
+
 
 LAYOUT_PLANAR, LAYOUT_C16 = 0, 1
 
@@ -289,6 +293,14 @@ def lib() -> ctypes.CDLL:
     L.v2ce_volume_loss_grads_workspace_bytes.restype = sz
     L.v2ce_volume_loss_grads.argtypes = [vp, vp, i32, i32, i32, i32, cp, sz, vp, vp, vp, sz, vp]
     L.v2ce_volume_loss_grads.restype = ctypes.c_int
+    L.v2ce_pred_head_fwd_workspace_bytes.argtypes = [i32] * 6
+    L.v2ce_pred_head_fwd_workspace_bytes.restype = sz
+    L.v2ce_pred_head_fwd.argtypes = [vp, vp, vp] + [i32] * 6 + [vp, vp, sz, vp]
+    L.v2ce_pred_head_fwd.restype = ctypes.c_int
+    L.v2ce_pred_head_grads_workspace_bytes.argtypes = [i32] * 6
+    L.v2ce_pred_head_grads_workspace_bytes.restype = sz
+    L.v2ce_pred_head_grads.argtypes = [vp, vp, vp, vp] + [i32] * 6 + [vp, vp, vp, vp, sz, vp]
+    L.v2ce_pred_head_grads.restype = ctypes.c_int
     L.v2ce_voxelize_batch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
     L.v2ce_voxelize_batch_workspace_bytes.restype = sz
     L.v2ce_voxelize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]

@@ -840,6 +840,17 @@ class V2ce3d(nn.Module):
         """x [B,L,2,H,W] f32 on the device -> [B,L,20,H,W] (contiguous; the reference returns the
         same values as a permuted view, v2ce_3d.py:29).  Like the reference, every call advances
         the spectral-norm u/v of the 12 SN layers by one power iteration."""
+        return self._guarded_forward(x, return_intermediates)
+
+    @torch.no_grad()
+    def forward_features(self, x: torch.Tensor) -> torch.Tensor:
+        """x [B,L,2,H,W] -> the last decoder block's output, the input of ``UNet.pred``, as the channels-last-16 tensor
+        [B,L,2,H,pitch,16] the head kernels take (pred_head.py; logical width in ``.lw``), without gradient.  The trunk
+        runs exactly as in ``forward`` -- the same spectral-norm power iteration (one per call), range-guard policy and
+        precision -- with the head not fused into the last convolution."""
+        return self._guarded_forward(x, False, features=True)
+
+    def _guarded_forward(self, x, return_intermediates, features=False):
         if x.dim() != 5 or x.shape[2] != self.in_channels:
             raise ValueError(f"expected x of shape [B,L,{self.in_channels},H,W], got {tuple(x.shape)}")
         x = hip.require_device_f32(x, "x")
@@ -847,9 +858,9 @@ class V2ce3d(nn.Module):
         # device current for the whole call (the ABI has no device argument, like a HIP stream call)
         with torch.cuda.device(x.device):
             if self.precision != "f16x2" or self.guard != "call":
-                return self._forward(x, return_intermediates)
+                return self._forward(x, return_intermediates, features=features)
             snap = self._sn_snapshot_fast()
-            out = self._forward(x, return_intermediates)
+            out = self._forward(x, return_intermediates, features=features)
             worst = float(self._prep["absmax"][:, :, 1].max().item())        # this call's bound (synchronises)
             if worst <= self.RANGE_GUARD_LIMIT:
                 return out
@@ -863,9 +874,11 @@ class V2ce3d(nn.Module):
             # (switching precision rebuilds the derived constants on the way in and out: a one-off for a checkpoint
             # that needs it on every call -- construct it with precision='f32' instead)
             with self.exact_f32():
-                return self._forward(x, return_intermediates)
+                return self._forward(x, return_intermediates, features=features)
 
-    def _forward(self, x, return_intermediates):
+    def _forward(self, x, return_intermediates, features=False):
+        """features=True: stop in front of UNet.pred and return its input (forward_features); the default launches are
+        today's."""
         if self._prep is None:
             self._prepare()
         P, U = self._prep, self.UNet
@@ -897,13 +910,16 @@ class V2ce3d(nn.Module):
         for i, blk in enumerate(U.resblocks):                                    # :349-350
             h = self._block(blk, P[f"res{i}"], h)
             inter[f"res{i}"] = self.to_planar(h) if return_intermediates else None
-        fuse = P["pred_fused"] if not return_intermediates else None
+        fuse = P["pred_fused"] if not (return_intermediates or features) else None
         for i, (blk, skip) in enumerate(zip(U.decoders, reversed(skips))):       # :357-365
             last = i == len(U.decoders) - 1
             h = self._block(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])),
                             pred=fuse if last else None)
             inter[f"dec{i}"] = self.to_planar(h) if return_intermediates else None
-        if fuse is not None:
+        if features:
+            # (the exact-f32 kernels produce planar tensors: one copy into the layout the head kernels take)
+            out = h if getattr(h, "c16", False) else self.to_c16(h)
+        elif fuse is not None:
             out = h                                                               # pred rode on dec3.conv2
         else:
             out = self._conv(h, None, *P["pred"], self.out_channels, 1, 1, hip.ACT_RELU, dense_out=True)   # :374
