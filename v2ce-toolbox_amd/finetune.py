@@ -93,6 +93,81 @@ def fit_head(model, image_units, gt_voxels, *, loss: Sequence[str] = losses.DEFA
     return history
 
 
+TAIL_GROUPS = ("pred", "conv2", "bn2")
+
+
+def fit_tail(model, image_units, gt_voxels, *, train: Sequence[str] = TAIL_GROUPS, loss: Sequence[str] = losses.DEFAULT_LOSS,
+             steps: int, lr: float, optimizer: str = "adam", cache_bytes: int = DEFAULT_CACHE_BYTES,
+             **loss_options) -> List[dict]:
+    """Fit the tail of the network -- the last decoder convolution ``UNet.decoders[3].conv2`` with its ``bn2``, and
+    ``UNet.pred`` -- to ground-truth voxels with everything in front of it frozen.
+
+    ``train`` names the parameter groups one optimizer steps: 'pred' (the head's weight and bias), 'conv2' (the
+    convolution's ``weight_bar``), 'bn2' (the BatchNorm's weight and bias; its statistics stay frozen).  The other
+    arguments and the returned history are those of ``fit_head``.
+
+    The two inputs of the convolution (``V2ce3d.forward_tail_inputs``) are computed once per window and kept while the
+    kept ones fit in ``cache_bytes``; every step is ``LastConv`` -> ``PredHead`` -> ``losses.calculate_loss`` ->
+    ``backward()`` -> one optimizer step.  As in the reference, every forward of the trained convolution advances its
+    spectral-norm u / v by one power iteration.  With neither 'conv2' nor 'bn2' in ``train`` the features in front of the
+    head are constant and this is ``fit_head``, step for step.
+
+    On return the model differs from its state on entry in the trained tensors and in conv2's ``weight_u`` /
+    ``weight_v``, which keep the iterations the fit applied; the other eleven spectral-norm layers and the call counter
+    are restored."""
+    from .last_conv import LastConv
+    train = tuple(train)
+    if not train or any(g not in TAIL_GROUPS for g in train) or len(set(train)) != len(train):
+        raise ValueError(f"train must be a non-empty subset of {TAIL_GROUPS}, got {train}")
+    if not ("conv2" in train or "bn2" in train):
+        return fit_head(model, image_units, gt_voxels, loss=loss, steps=steps, lr=lr, optimizer=optimizer,
+                        cache_bytes=cache_bytes, **loss_options)
+    loss = losses.check_loss_names(loss)
+    if optimizer not in ("adam", "sgd"):
+        raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
+    if int(steps) < 0:
+        raise ValueError(f"steps must be >= 0, got {steps}")
+    windows = _windows(image_units, gt_voxels)
+    head, conv = PredHead.from_model(model), LastConv.from_model(model)
+    groups = {"pred": [head.weight, head.bias], "conv2": [conv.weight_bar], "bn2": [conv.bn_weight, conv.bn_bias]}
+    for g, ps in groups.items():
+        for p in ps:
+            p.requires_grad_(g in train)
+    opt = (torch.optim.Adam if optimizer == "adam" else torch.optim.SGD)([p for g in train for p in groups[g]], lr=lr)
+    snap = model.sn_snapshot()
+    cache, used = {}, 0
+
+    def inputs(i):
+        nonlocal used
+        if i in cache:
+            return cache[i]
+        model.sn_restore(snap)
+        t, res = model.forward_tail_inputs(windows[i][0])
+        nb = (t.numel() + res.numel()) * 4
+        if used + nb <= cache_bytes:
+            cache[i], used = (t, res), used + nb
+        return t, res
+
+    history = []
+    try:
+        for k in range(int(steps)):
+            i = k % len(windows)
+            opt.zero_grad(set_to_none=True)
+            pred = head(conv(*inputs(i)))
+            total, d = losses.calculate_loss(pred, windows[i][1].contiguous(), loss=loss, **loss_options)
+            total.backward()
+            opt.step()
+            history.append({"loss": float(total.detach()), "loss_dict": {n: float(v) for n, v in d.items()}})
+    finally:
+        model.sn_restore(snap)
+    if model.precision == "f16x2" and float(conv.guard) > model.RANGE_GUARD_LIMIT:
+        logger.warning(f"split-half range guard of the trained convolution: bound {float(conv.guard):.3e} > "
+                       f"{model.RANGE_GUARD_LIMIT:.1e}; fit with precision='f32'")
+    head.write_back(model)
+    conv.write_back(model)
+    return history
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # command line
 
@@ -127,6 +202,8 @@ def build_parser():
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--optimizer", default="adam", choices=("adam", "sgd"))
+    p.add_argument("--train", default="head", choices=("head", "tail"),
+                   help="head: UNet.pred alone (fit_head); tail: the last decoder convolution, its bn2 and UNet.pred (fit_tail)")
     p.add_argument("--cache_gb", type=float, default=DEFAULT_CACHE_BYTES / 2 ** 30, help="feature cache budget")
     p.add_argument("-o", "--out", type=str, default="./tuned.pt", help="the tuned state_dict (v2ce.py -m loads it)")
     p.add_argument("--history", type=str, default=None, help="the per-step history as JSON (default: <out>.history.json)")
@@ -194,8 +271,9 @@ def main(argv=None):
     names = tuple(args.losses) if args.losses else losses.DEFAULT_LOSS
     opts = {k: getattr(args, k) for k in ("ef_type", "add_base_loss", "alpha_pyramid", "alpha_ef", "alpha_efc",
                                           "alpha_match", "alpha_compensation", "alpha_pt", "alpha_norm")}
-    history = fit_head(model, xs, gs, loss=names, steps=args.steps, lr=args.lr, optimizer=args.optimizer,
-                       cache_bytes=int(args.cache_gb * 2 ** 30), **opts)
+    fit = fit_tail if args.train == "tail" else fit_head
+    history = fit(model, xs, gs, loss=names, steps=args.steps, lr=args.lr, optimizer=args.optimizer,
+                  cache_bytes=int(args.cache_gb * 2 ** 30), **opts)
     os.makedirs(op.dirname(op.abspath(args.out)), exist_ok=True)
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, args.out)
     hist_path = args.history or args.out + ".history.json"

@@ -52,6 +52,10 @@ GRAD_EXPORTS = ("v2ce_voxloss_grads_workspace_bytes", "v2ce_voxloss_grads", "v2c
 TRAIN_EXPORTS = ("v2ce_pred_head_fwd_workspace_bytes", "v2ce_pred_head_fwd", "v2ce_pred_head_grads_workspace_bytes",
                  "v2ce_pred_head_grads")
 
+# the weight gradients of the trunk's convolutions (include/v2ce_hip_convgrad.h)
+CONVGRAD_EXPORTS = ("v2ce_conv32_wgrad_workspace_bytes", "v2ce_conv32_wgrad")
+WGRAD_CHAIN = 4096                       # V2CE_WGRAD_CHAIN: positions one f32 accumulator sums before it meets the f64 sum
+
 
 LAYOUT_PLANAR, LAYOUT_C16 = 0, 1
 
@@ -301,6 +305,10 @@ def lib() -> ctypes.CDLL:
     L.v2ce_pred_head_grads_workspace_bytes.restype = sz
     L.v2ce_pred_head_grads.argtypes = [vp, vp, vp, vp] + [i32] * 6 + [vp, vp, vp, vp, sz, vp]
     L.v2ce_pred_head_grads.restype = ctypes.c_int
+    L.v2ce_conv32_wgrad_workspace_bytes.argtypes = [i32] * 6
+    L.v2ce_conv32_wgrad_workspace_bytes.restype = sz
+    L.v2ce_conv32_wgrad.argtypes = [vp, vp, vp] + [i32] * 5 + [vp, vp, vp, sz, i32, vp]
+    L.v2ce_conv32_wgrad.restype = ctypes.c_int
     L.v2ce_voxelize_batch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
     L.v2ce_voxelize_batch_workspace_bytes.restype = sz
     L.v2ce_voxelize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]

@@ -779,6 +779,22 @@ class V2ce3d(nn.Module):
         return self._conv(t, None, w2, *bn2, blk.cout, 3, 1, hip.ACT_RELU, residual=res,
                           split=self._split(blk.cout, blk.cout), track=track and pred is None, pred=pred)
 
+    def _block_inputs(self, blk: _ResidualBlock3D, d, x0, x1=None, up_to=None):
+        """What ``_block`` hands to conv2, by the launches ``_block`` itself makes in front of it: (relu(bn1(conv1 x)),
+        bn_d(conv_d x)) -- one launch where the shortcut rides on conv1, else the two of the unfused branch.  A block whose
+        shortcut is folded into conv2's K loop has no such pair."""
+        s = blk.stride_hw
+        bn1 = d.get("bn1_eff", d["bn1"])
+        if self._fuse_shortcut(blk):
+            return self._conv(x0, x1, d["conv1_w"], *bn1, blk.cout, 3, s, hip.ACT_RELU, up_to=up_to, split=True,
+                              sc=(d["down_w"], *d["down_bn"]))
+        assert d.get("fold") is None, "the block's shortcut is folded into conv2: it has no separate residual"
+        t = self._conv(x0, x1, d["conv1_w"], *bn1, blk.cout, 3, s, hip.ACT_RELU, up_to=up_to,
+                       split=self._split(blk.cin, blk.cout))
+        res = self._conv(x0, x1, d["down_w"], *d["down_bn"], blk.cout, 1, s, hip.ACT_NONE, up_to=up_to,
+                         split=self._split(blk.cin, blk.cout, 1, s))
+        return t, res
+
     @torch.no_grad()
     def advance_spectral_norm(self):
         """Apply the power iteration of one forward call to all 12 SN layers without running the
@@ -850,6 +866,18 @@ class V2ce3d(nn.Module):
         precision -- with the head not fused into the last convolution."""
         return self._guarded_forward(x, False, features=True)
 
+    @torch.no_grad()
+    def forward_tail_inputs(self, x: torch.Tensor):
+        """x [B,L,2,H,W] -> (t, res): the two tensors the last decoder block's conv2 launch reads -- t = relu(bn1(conv1(.))),
+        its input, and res = bn_d(conv_d(.)), the block's shortcut branch -- both channels-last-16 [B,L,2,H,pitch,16] with
+        the logical width in ``.lw``, without gradient (last_conv.py: ``LastConv`` turns them into ``forward_features``'s
+        tensor).  The trunk runs exactly as in ``forward_features`` -- the same spectral-norm power iteration (one per
+        call, conv2's included), range-guard policy and precision -- and stops in front of conv2."""
+        t, res = self._guarded_forward(x, False, features="tail")
+        if hasattr(t, "absmax"):        # the range slot is a view of a table the next call clears: keep this call's value
+            t.absmax = t.absmax.clone()
+        return t, res
+
     def _guarded_forward(self, x, return_intermediates, features=False):
         if x.dim() != 5 or x.shape[2] != self.in_channels:
             raise ValueError(f"expected x of shape [B,L,{self.in_channels},H,W], got {tuple(x.shape)}")
@@ -877,8 +905,8 @@ class V2ce3d(nn.Module):
                 return self._forward(x, return_intermediates, features=features)
 
     def _forward(self, x, return_intermediates, features=False):
-        """features=True: stop in front of UNet.pred and return its input (forward_features); the default launches are
-        today's."""
+        """features=True: stop in front of UNet.pred and return its input (forward_features); features="tail": stop in front
+        of the last decoder block's conv2 and return its two inputs (forward_tail_inputs); the default launches are today's."""
         if self._prep is None:
             self._prepare()
         P, U = self._prep, self.UNet
@@ -913,10 +941,15 @@ class V2ce3d(nn.Module):
         fuse = P["pred_fused"] if not (return_intermediates or features) else None
         for i, (blk, skip) in enumerate(zip(U.decoders, reversed(skips))):       # :357-365
             last = i == len(U.decoders) - 1
+            if last and features == "tail":
+                h = self._block_inputs(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])))
+                break
             h = self._block(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])),
                             pred=fuse if last else None)
             inter[f"dec{i}"] = self.to_planar(h) if return_intermediates else None
-        if features:
+        if features == "tail":
+            out = tuple(a if getattr(a, "c16", False) else self.to_c16(a) for a in h)
+        elif features:
             # (the exact-f32 kernels produce planar tensors: one copy into the layout the head kernels take)
             out = h if getattr(h, "c16", False) else self.to_c16(h)
         elif fuse is not None:
