@@ -168,6 +168,83 @@ def fit_tail(model, image_units, gt_voxels, *, train: Sequence[str] = TAIL_GROUP
     return history
 
 
+TAIL_NORM_GROUPS = TAIL_GROUPS + ("bn1", "bnd")
+
+
+def fit_tail_norms(model, image_units, gt_voxels, *, train: Sequence[str] = TAIL_NORM_GROUPS,
+                   loss: Sequence[str] = losses.DEFAULT_LOSS, steps: int, lr: float, optimizer: str = "adam",
+                   cache_bytes: int = DEFAULT_CACHE_BYTES, **loss_options) -> List[dict]:
+    """Fit the whole affine tail of the last decoder block: what ``fit_tail`` trains, and the affine parameters of the
+    block's other two BatchNorms -- ``bn1`` behind conv1 and ``downsample.1`` on the shortcut -- whose gradients pass
+    through conv2 (``v2ce_conv32_dgrad``).
+
+    ``train`` names the parameter groups one optimizer steps: those of ``fit_tail`` ('pred', 'conv2', 'bn2'), 'bn1' and
+    'bnd' (weight and bias each; the statistics stay frozen).  The other arguments and the returned history are those
+    of ``fit_tail``.  With neither 'bn1' nor 'bnd' in ``train`` this is ``fit_tail`` with the same arguments, step for
+    step.
+
+    The normalised, pre-affine pair in front of the two BatchNorms' affine parts (``V2ce3d.forward_tail_normed``) is
+    computed once per window and kept while the kept ones fit in ``cache_bytes``; every step is ``TailNorms`` ->
+    ``LastConv`` -> ``PredHead`` -> ``losses.calculate_loss`` -> ``backward()`` -> one optimizer step.
+
+    On return the model differs from its state on entry in the trained tensors and in conv2's ``weight_u`` /
+    ``weight_v``, which keep the iterations the fit applied; the other eleven spectral-norm layers and the call counter
+    are restored."""
+    from .last_conv import LastConv, TailNorms
+    train = tuple(train)
+    if not train or any(g not in TAIL_NORM_GROUPS for g in train) or len(set(train)) != len(train):
+        raise ValueError(f"train must be a non-empty subset of {TAIL_NORM_GROUPS}, got {train}")
+    if not ("bn1" in train or "bnd" in train):
+        return fit_tail(model, image_units, gt_voxels, train=train, loss=loss, steps=steps, lr=lr, optimizer=optimizer,
+                        cache_bytes=cache_bytes, **loss_options)
+    loss = losses.check_loss_names(loss)
+    if optimizer not in ("adam", "sgd"):
+        raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
+    if int(steps) < 0:
+        raise ValueError(f"steps must be >= 0, got {steps}")
+    windows = _windows(image_units, gt_voxels)
+    head, conv, norms = PredHead.from_model(model), LastConv.from_model(model), TailNorms.from_model(model)
+    groups = {"pred": [head.weight, head.bias], "conv2": [conv.weight_bar], "bn2": [conv.bn_weight, conv.bn_bias],
+              "bn1": [norms.bn1_weight, norms.bn1_bias], "bnd": [norms.bnd_weight, norms.bnd_bias]}
+    for g, ps in groups.items():
+        for p in ps:
+            p.requires_grad_(g in train)
+    opt = (torch.optim.Adam if optimizer == "adam" else torch.optim.SGD)([p for g in train for p in groups[g]], lr=lr)
+    snap = model.sn_snapshot()
+    cache, used = {}, 0
+
+    def inputs(i):
+        nonlocal used
+        if i in cache:
+            return cache[i]
+        model.sn_restore(snap)
+        z1, zd = model.forward_tail_normed(windows[i][0])
+        nb = (z1.numel() + zd.numel()) * 4
+        if used + nb <= cache_bytes:
+            cache[i], used = (z1, zd), used + nb
+        return z1, zd
+
+    history = []
+    try:
+        for k in range(int(steps)):
+            i = k % len(windows)
+            opt.zero_grad(set_to_none=True)
+            pred = head(conv(*norms(*inputs(i))))
+            total, d = losses.calculate_loss(pred, windows[i][1].contiguous(), loss=loss, **loss_options)
+            total.backward()
+            opt.step()
+            history.append({"loss": float(total.detach()), "loss_dict": {n: float(v) for n, v in d.items()}})
+    finally:
+        model.sn_restore(snap)
+    if model.precision == "f16x2" and float(conv.guard) > model.RANGE_GUARD_LIMIT:
+        logger.warning(f"split-half range guard of the trained convolution: bound {float(conv.guard):.3e} > "
+                       f"{model.RANGE_GUARD_LIMIT:.1e}; fit with precision='f32'")
+    head.write_back(model)
+    conv.write_back(model)
+    norms.write_back(model)
+    return history
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # command line
 
@@ -202,8 +279,9 @@ def build_parser():
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--optimizer", default="adam", choices=("adam", "sgd"))
-    p.add_argument("--train", default="head", choices=("head", "tail"),
-                   help="head: UNet.pred alone (fit_head); tail: the last decoder convolution, its bn2 and UNet.pred (fit_tail)")
+    p.add_argument("--train", default="head", choices=("head", "tail", "tail_norms"),
+                   help="head: UNet.pred alone (fit_head); tail: the last decoder convolution, its bn2 and UNet.pred (fit_tail); "
+                        "tail_norms: those and the last decoder block's bn1 and downsample.1 (fit_tail_norms)")
     p.add_argument("--cache_gb", type=float, default=DEFAULT_CACHE_BYTES / 2 ** 30, help="feature cache budget")
     p.add_argument("-o", "--out", type=str, default="./tuned.pt", help="the tuned state_dict (v2ce.py -m loads it)")
     p.add_argument("--history", type=str, default=None, help="the per-step history as JSON (default: <out>.history.json)")
@@ -271,7 +349,7 @@ def main(argv=None):
     names = tuple(args.losses) if args.losses else losses.DEFAULT_LOSS
     opts = {k: getattr(args, k) for k in ("ef_type", "add_base_loss", "alpha_pyramid", "alpha_ef", "alpha_efc",
                                           "alpha_match", "alpha_compensation", "alpha_pt", "alpha_norm")}
-    fit = fit_tail if args.train == "tail" else fit_head
+    fit = {"head": fit_head, "tail": fit_tail, "tail_norms": fit_tail_norms}[args.train]
     history = fit(model, xs, gs, loss=names, steps=args.steps, lr=args.lr, optimizer=args.optimizer,
                   cache_bytes=int(args.cache_gb * 2 ** 30), **opts)
     os.makedirs(op.dirname(op.abspath(args.out)), exist_ok=True)

@@ -56,6 +56,10 @@ TRAIN_EXPORTS = ("v2ce_pred_head_fwd_workspace_bytes", "v2ce_pred_head_fwd", "v2
 CONVGRAD_EXPORTS = ("v2ce_conv32_wgrad_workspace_bytes", "v2ce_conv32_wgrad")
 WGRAD_CHAIN = 4096                       # V2CE_WGRAD_CHAIN: positions one f32 accumulator sums before it meets the f64 sum
 
+# the input gradients of the trunk's convolutions (include/v2ce_hip_convdgrad.h)
+CONVDGRAD_EXPORTS = ("v2ce_conv32_dgrad_workspace_bytes", "v2ce_conv32_dgrad")
+DGRAD_TERMS = 864                        # V2CE_DGRAD_TERMS: f32 terms of one d_x element (32 output channels x 27 taps)
+
 
 LAYOUT_PLANAR, LAYOUT_C16 = 0, 1
 
@@ -309,6 +313,10 @@ def lib() -> ctypes.CDLL:
     L.v2ce_conv32_wgrad_workspace_bytes.restype = sz
     L.v2ce_conv32_wgrad.argtypes = [vp, vp, vp] + [i32] * 5 + [vp, vp, vp, sz, i32, vp]
     L.v2ce_conv32_wgrad.restype = ctypes.c_int
+    L.v2ce_conv32_dgrad_workspace_bytes.argtypes = [i32] * 6
+    L.v2ce_conv32_dgrad_workspace_bytes.restype = sz
+    L.v2ce_conv32_dgrad.argtypes = [vp, vp, vp] + [i32] * 5 + [vp, vp, vp, sz, i32, vp]
+    L.v2ce_conv32_dgrad.restype = ctypes.c_int
     L.v2ce_voxelize_batch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
     L.v2ce_voxelize_batch_workspace_bytes.restype = sz
     L.v2ce_voxelize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]

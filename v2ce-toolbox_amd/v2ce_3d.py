@@ -779,21 +779,49 @@ class V2ce3d(nn.Module):
         return self._conv(t, None, w2, *bn2, blk.cout, 3, 1, hip.ACT_RELU, residual=res,
                           split=self._split(blk.cout, blk.cout), track=track and pred is None, pred=pred)
 
-    def _block_inputs(self, blk: _ResidualBlock3D, d, x0, x1=None, up_to=None):
+    def _block_inputs(self, blk: _ResidualBlock3D, d, x0, x1=None, up_to=None, normed=False):
         """What ``_block`` hands to conv2, by the launches ``_block`` itself makes in front of it: (relu(bn1(conv1 x)),
         bn_d(conv_d x)) -- one launch where the shortcut rides on conv1, else the two of the unfused branch.  A block whose
-        shortcut is folded into conv2's K loop has no such pair."""
+        shortcut is folded into conv2's K loop has no such pair.  ``normed``: the same launches without activation and with
+        epilogue vectors that leave the two BatchNorms' affine parts out (``_normed_epilogues``): the normalised,
+        pre-affine pair (z1, zd) of ``forward_tail_normed``."""
         s = blk.stride_hw
-        bn1 = d.get("bn1_eff", d["bn1"])
+        bn1, down_bn, act = d.get("bn1_eff", d["bn1"]), d["down_bn"], hip.ACT_RELU
+        if normed:
+            bn1, down_bn = self._normed_epilogues(blk, d)
+            act = hip.ACT_NONE
         if self._fuse_shortcut(blk):
-            return self._conv(x0, x1, d["conv1_w"], *bn1, blk.cout, 3, s, hip.ACT_RELU, up_to=up_to, split=True,
-                              sc=(d["down_w"], *d["down_bn"]))
+            return self._conv(x0, x1, d["conv1_w"], *bn1, blk.cout, 3, s, act, up_to=up_to, split=True,
+                              sc=(d["down_w"], *down_bn))
         assert d.get("fold") is None, "the block's shortcut is folded into conv2: it has no separate residual"
-        t = self._conv(x0, x1, d["conv1_w"], *bn1, blk.cout, 3, s, hip.ACT_RELU, up_to=up_to,
+        t = self._conv(x0, x1, d["conv1_w"], *bn1, blk.cout, 3, s, act, up_to=up_to,
                        split=self._split(blk.cin, blk.cout))
-        res = self._conv(x0, x1, d["down_w"], *d["down_bn"], blk.cout, 1, s, hip.ACT_NONE, up_to=up_to,
+        res = self._conv(x0, x1, d["down_w"], *down_bn, blk.cout, 1, s, hip.ACT_NONE, up_to=up_to,
                          split=self._split(blk.cin, blk.cout, 1, s))
         return t, res
+
+    def _normed_epilogues(self, blk, d):
+        """-> ((scale1, shift1), (scale_d, shift_d)): the epilogue vectors with which conv1's launch gives (conv1(.) / sigma -
+        mean1) rsqrt(var1 + eps) and the shortcut's gives (conv_d(.) + bias_d - mean_d) rsqrt(var_d + eps).  They are built
+        from the statistics, never from a folded scale divided by the BatchNorm's weight (which may be zero).  Where the
+        planes of W_bar were packed once (``sn_once``), 1 / sigma of this call's power iteration rides in conv1's scale."""
+        if "normed" not in d:
+            bnd, bias_d = blk.downsample[1], blk.downsample[0].bias
+            rs1 = (1.0 / torch.sqrt(blk.bn1.running_var + BN_EPS)).float().contiguous()
+            rsd = (1.0 / torch.sqrt(bnd.running_var + BN_EPS)).float().contiguous()
+            shift_d = -bnd.running_mean * rsd if bias_d is None else (bias_d - bnd.running_mean) * rsd
+            d["normed"] = (rs1, (-blk.bn1.running_mean * rs1).float().contiguous(), rsd, shift_d.float().contiguous())
+        rs1, shift1, rsd, shift_d = d["normed"]
+        once = self._prep.get("sn_once")
+        if once is not None and "bn1_eff" in d:
+            k = 0                                            # this block's conv1 in the order of the batched power iteration
+            for blocks in (self.UNet.resblocks, self.UNet.decoders):
+                for b in blocks:
+                    if b is blk:
+                        return (rs1 * once["inv_sigma"][k], shift1), (rsd, shift_d)
+                    k += 2 if b.sn else 0
+            raise AssertionError("the block is not one of the spectral-norm blocks")
+        return (rs1, shift1), (rsd, shift_d)
 
     @torch.no_grad()
     def advance_spectral_norm(self):
@@ -878,6 +906,17 @@ class V2ce3d(nn.Module):
             t.absmax = t.absmax.clone()
         return t, res
 
+    @torch.no_grad()
+    def forward_tail_normed(self, x: torch.Tensor):
+        """x [B,L,2,H,W] -> (z1, zd): the normalised, pre-affine outputs of the last decoder block's first half -- z1 =
+        (conv1(.) / sigma - mean1) rsqrt(var1 + eps) and zd = (conv_d(.) + bias_d - mean_d) rsqrt(var_d + eps) -- both
+        channels-last-16 [B,L,2,H,pitch,16] with the logical width in ``.lw``, without gradient (last_conv.py:
+        ``TailNorms`` turns them into ``forward_tail_inputs``'s pair: t = relu(bn1.weight z1 + bn1.bias), res =
+        bn_d.weight zd + bn_d.bias).  The trunk runs exactly as in ``forward_tail_inputs`` -- the same launches, power
+        iteration (one per call), range-guard policy and precision; only the epilogue vectors and the activation of
+        the block's first launches differ."""
+        return self._guarded_forward(x, False, features="normed")
+
     def _guarded_forward(self, x, return_intermediates, features=False):
         if x.dim() != 5 or x.shape[2] != self.in_channels:
             raise ValueError(f"expected x of shape [B,L,{self.in_channels},H,W], got {tuple(x.shape)}")
@@ -906,7 +945,8 @@ class V2ce3d(nn.Module):
 
     def _forward(self, x, return_intermediates, features=False):
         """features=True: stop in front of UNet.pred and return its input (forward_features); features="tail": stop in front
-        of the last decoder block's conv2 and return its two inputs (forward_tail_inputs); the default launches are today's."""
+        of the last decoder block's conv2 and return its two inputs (forward_tail_inputs); features="normed": the same two launches
+        without the BatchNorms' affine parts and the relu (forward_tail_normed); the default launches are today's."""
         if self._prep is None:
             self._prepare()
         P, U = self._prep, self.UNet
@@ -941,13 +981,14 @@ class V2ce3d(nn.Module):
         fuse = P["pred_fused"] if not (return_intermediates or features) else None
         for i, (blk, skip) in enumerate(zip(U.decoders, reversed(skips))):       # :357-365
             last = i == len(U.decoders) - 1
-            if last and features == "tail":
-                h = self._block_inputs(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])))
+            if last and features in ("tail", "normed"):
+                h = self._block_inputs(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])),
+                                       normed=features == "normed")
                 break
             h = self._block(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])),
                             pred=fuse if last else None)
             inter[f"dec{i}"] = self.to_planar(h) if return_intermediates else None
-        if features == "tail":
+        if features in ("tail", "normed"):
             out = tuple(a if getattr(a, "c16", False) else self.to_c16(a) for a in h)
         elif features:
             # (the exact-f32 kernels produce planar tensors: one copy into the layout the head kernels take)
