@@ -245,6 +245,90 @@ def fit_tail_norms(model, image_units, gt_voxels, *, train: Sequence[str] = TAIL
     return history
 
 
+LAST_BLOCK_GROUPS = TAIL_NORM_GROUPS + ("conv1", "convd")
+
+
+def fit_last_block(model, image_units, gt_voxels, *, train: Sequence[str] = LAST_BLOCK_GROUPS,
+                   loss: Sequence[str] = losses.DEFAULT_LOSS, steps: int, lr: float, optimizer: str = "adam",
+                   cache_bytes: int = DEFAULT_CACHE_BYTES, **loss_options) -> List[dict]:
+    """Fit the whole last decoder block ``UNet.decoders[3]`` and ``UNet.pred``: what ``fit_tail_norms`` trains, the block's
+    spectral-normalised 3x3x3 ``conv1`` and its 1x1x1 shortcut convolution ``downsample.0``, whose weight gradients read
+    the block's upsample + concat input without materialising it (``v2ce_convup_wgrad``).
+
+    ``train`` names the parameter groups one optimizer steps: those of ``fit_tail_norms`` ('pred', 'conv2', 'bn2', 'bn1',
+    'bnd'), 'conv1' (the convolution's ``weight_bar``) and 'convd' (the shortcut's weight and, where the model has one,
+    bias).  The other arguments and the returned history are those of ``fit_tail_norms``.  With neither 'conv1' nor
+    'convd' in ``train`` this is ``fit_tail_norms`` with the same arguments, step for step.
+
+    The block's two sources (``V2ce3d.forward_tail_sources``) are computed once per window and kept while the kept ones
+    fit in ``cache_bytes``; every step is ``TailConvs`` -> ``TailNorms`` -> ``LastConv`` -> ``PredHead`` ->
+    ``losses.calculate_loss`` -> ``backward()`` -> one optimizer step.  As in the reference, every forward of a trained
+    convolution advances its spectral-norm u / v by one power iteration.
+
+    On return the model differs from its state on entry in the trained tensors and in the ``weight_u`` / ``weight_v`` of
+    the block's conv1 and conv2, which keep the iterations the fit applied; the other ten spectral-norm layers and the
+    call counter are restored."""
+    from .last_block import TailConvs
+    from .last_conv import LastConv, TailNorms
+    train = tuple(train)
+    if not train or any(g not in LAST_BLOCK_GROUPS for g in train) or len(set(train)) != len(train):
+        raise ValueError(f"train must be a non-empty subset of {LAST_BLOCK_GROUPS}, got {train}")
+    if not ("conv1" in train or "convd" in train):
+        return fit_tail_norms(model, image_units, gt_voxels, train=train, loss=loss, steps=steps, lr=lr, optimizer=optimizer,
+                              cache_bytes=cache_bytes, **loss_options)
+    loss = losses.check_loss_names(loss)
+    if optimizer not in ("adam", "sgd"):
+        raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
+    if int(steps) < 0:
+        raise ValueError(f"steps must be >= 0, got {steps}")
+    windows = _windows(image_units, gt_voxels)
+    head, conv, norms = PredHead.from_model(model), LastConv.from_model(model), TailNorms.from_model(model)
+    convs = TailConvs.from_model(model)
+    groups = {"pred": [head.weight, head.bias], "conv2": [conv.weight_bar], "bn2": [conv.bn_weight, conv.bn_bias],
+              "bn1": [norms.bn1_weight, norms.bn1_bias], "bnd": [norms.bnd_weight, norms.bnd_bias],
+              "conv1": [convs.weight_bar],
+              "convd": [convs.short_weight] + ([convs.short_bias] if convs.short_bias is not None else [])}
+    for g, ps in groups.items():
+        for p in ps:
+            p.requires_grad_(g in train)
+    opt = (torch.optim.Adam if optimizer == "adam" else torch.optim.SGD)([p for g in train for p in groups[g]], lr=lr)
+    snap = model.sn_snapshot()
+    cache, used = {}, 0
+
+    def inputs(i):
+        nonlocal used
+        if i in cache:
+            return cache[i]
+        model.sn_restore(snap)
+        x0, x1 = model.forward_tail_sources(windows[i][0])
+        nb = (x0.numel() + x1.numel()) * 4
+        if used + nb <= cache_bytes:
+            cache[i], used = (x0, x1), used + nb
+        return x0, x1
+
+    history = []
+    try:
+        for k in range(int(steps)):
+            i = k % len(windows)
+            opt.zero_grad(set_to_none=True)
+            pred = head(conv(*norms(*convs(*inputs(i)))))
+            total, d = losses.calculate_loss(pred, windows[i][1].contiguous(), loss=loss, **loss_options)
+            total.backward()
+            opt.step()
+            history.append({"loss": float(total.detach()), "loss_dict": {n: float(v) for n, v in d.items()}})
+    finally:
+        model.sn_restore(snap)
+    bound = max(float(conv.guard), float(convs.guard))
+    if model.precision == "f16x2" and bound > model.RANGE_GUARD_LIMIT:
+        logger.warning(f"split-half range guard of the trained convolutions: bound {bound:.3e} > "
+                       f"{model.RANGE_GUARD_LIMIT:.1e}; fit with precision='f32'")
+    head.write_back(model)
+    conv.write_back(model)
+    norms.write_back(model)
+    convs.write_back(model)
+    return history
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # command line
 
@@ -279,9 +363,11 @@ def build_parser():
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--optimizer", default="adam", choices=("adam", "sgd"))
-    p.add_argument("--train", default="head", choices=("head", "tail", "tail_norms"),
+    p.add_argument("--train", default="head", choices=("head", "tail", "tail_norms", "last_block"),
                    help="head: UNet.pred alone (fit_head); tail: the last decoder convolution, its bn2 and UNet.pred (fit_tail); "
-                        "tail_norms: those and the last decoder block's bn1 and downsample.1 (fit_tail_norms)")
+                        "tail_norms: those and the last decoder block's bn1 and downsample.1 (fit_tail_norms); "
+                        "last_block: those and the block's conv1 and shortcut convolution, the whole last decoder block "
+                        "(fit_last_block)")
     p.add_argument("--cache_gb", type=float, default=DEFAULT_CACHE_BYTES / 2 ** 30, help="feature cache budget")
     p.add_argument("-o", "--out", type=str, default="./tuned.pt", help="the tuned state_dict (v2ce.py -m loads it)")
     p.add_argument("--history", type=str, default=None, help="the per-step history as JSON (default: <out>.history.json)")
@@ -349,7 +435,7 @@ def main(argv=None):
     names = tuple(args.losses) if args.losses else losses.DEFAULT_LOSS
     opts = {k: getattr(args, k) for k in ("ef_type", "add_base_loss", "alpha_pyramid", "alpha_ef", "alpha_efc",
                                           "alpha_match", "alpha_compensation", "alpha_pt", "alpha_norm")}
-    fit = {"head": fit_head, "tail": fit_tail, "tail_norms": fit_tail_norms}[args.train]
+    fit = {"head": fit_head, "tail": fit_tail, "tail_norms": fit_tail_norms, "last_block": fit_last_block}[args.train]
     history = fit(model, xs, gs, loss=names, steps=args.steps, lr=args.lr, optimizer=args.optimizer,
                   cache_bytes=int(args.cache_gb * 2 ** 30), **opts)
     os.makedirs(op.dirname(op.abspath(args.out)), exist_ok=True)

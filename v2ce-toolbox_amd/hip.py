@@ -60,6 +60,11 @@ WGRAD_CHAIN = 4096                       # V2CE_WGRAD_CHAIN: positions one f32 a
 CONVDGRAD_EXPORTS = ("v2ce_conv32_dgrad_workspace_bytes", "v2ce_conv32_dgrad")
 DGRAD_TERMS = 864                        # V2CE_DGRAD_TERMS: f32 terms of one d_x element (32 output channels x 27 taps)
 
+# the weight gradients of the last decoder block's conv1 and shortcut on the upsample + concat input
+# (include/v2ce_hip_convupgrad.h)
+CONVUPGRAD_EXPORTS = ("v2ce_convup_wgrad_workspace_bytes", "v2ce_convup_wgrad")
+UPWGRAD_CHAIN = 4096                     # V2CE_UPWGRAD_CHAIN: positions one f32 accumulator sums before it meets the f64 sum
+
 
 LAYOUT_PLANAR, LAYOUT_C16 = 0, 1
 
@@ -317,6 +322,10 @@ def lib() -> ctypes.CDLL:
     L.v2ce_conv32_dgrad_workspace_bytes.restype = sz
     L.v2ce_conv32_dgrad.argtypes = [vp, vp, vp] + [i32] * 5 + [vp, vp, vp, sz, i32, vp]
     L.v2ce_conv32_dgrad.restype = ctypes.c_int
+    L.v2ce_convup_wgrad_workspace_bytes.argtypes = [i32] * 7
+    L.v2ce_convup_wgrad_workspace_bytes.restype = sz
+    L.v2ce_convup_wgrad.argtypes = [vp, vp, vp, vp] + [i32] * 6 + [vp, vp, vp, vp, sz, i32, vp]
+    L.v2ce_convup_wgrad.restype = ctypes.c_int
     L.v2ce_voxelize_batch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
     L.v2ce_voxelize_batch_workspace_bytes.restype = sz
     L.v2ce_voxelize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]

@@ -917,6 +917,20 @@ class V2ce3d(nn.Module):
         the block's first launches differ."""
         return self._guarded_forward(x, False, features="normed")
 
+    @torch.no_grad()
+    def forward_tail_sources(self, x: torch.Tensor):
+        """x [B,L,2,H,W] -> (x0, x1): the two tensors the last decoder block reads -- x0, the output of the decoder in front
+        of it (64 channels at half the resolution, [B,L,4,H0,pitch0,16]), which the block upsamples, and x1, the skip
+        tensor (32 channels, [B,L,2,H,pitch,16]) -- both channels-last-16 with the logical width in ``.lw``, without
+        gradient (last_block.py: ``TailConvs`` turns them into ``forward_tail_normed``'s pair).  The trunk runs exactly as
+        in ``forward_tail_inputs`` -- the same spectral-norm power iteration (one per call, the last block's included),
+        range-guard policy and precision -- and stops in front of the last decoder block."""
+        x0, x1 = self._guarded_forward(x, False, features="sources")
+        for a in (x0, x1):              # the range slots are views of a table the next call clears: keep this call's values
+            if hasattr(a, "absmax"):
+                a.absmax = a.absmax.clone()
+        return x0, x1
+
     def _guarded_forward(self, x, return_intermediates, features=False):
         if x.dim() != 5 or x.shape[2] != self.in_channels:
             raise ValueError(f"expected x of shape [B,L,{self.in_channels},H,W], got {tuple(x.shape)}")
@@ -946,7 +960,8 @@ class V2ce3d(nn.Module):
     def _forward(self, x, return_intermediates, features=False):
         """features=True: stop in front of UNet.pred and return its input (forward_features); features="tail": stop in front
         of the last decoder block's conv2 and return its two inputs (forward_tail_inputs); features="normed": the same two launches
-        without the BatchNorms' affine parts and the relu (forward_tail_normed); the default launches are today's."""
+        without the BatchNorms' affine parts and the relu (forward_tail_normed); features="sources": stop in front of the last decoder
+        block and return the two tensors it reads (forward_tail_sources); the default launches are today's."""
         if self._prep is None:
             self._prepare()
         P, U = self._prep, self.UNet
@@ -981,6 +996,9 @@ class V2ce3d(nn.Module):
         fuse = P["pred_fused"] if not (return_intermediates or features) else None
         for i, (blk, skip) in enumerate(zip(U.decoders, reversed(skips))):       # :357-365
             last = i == len(U.decoders) - 1
+            if last and features == "sources":
+                h = (h, skip)
+                break
             if last and features in ("tail", "normed"):
                 h = self._block_inputs(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])),
                                        normed=features == "normed")
@@ -988,7 +1006,7 @@ class V2ce3d(nn.Module):
             h = self._block(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])),
                             pred=fuse if last else None)
             inter[f"dec{i}"] = self.to_planar(h) if return_intermediates else None
-        if features in ("tail", "normed"):
+        if features in ("tail", "normed", "sources"):
             out = tuple(a if getattr(a, "c16", False) else self.to_c16(a) for a in h)
         elif features:
             # (the exact-f32 kernels produce planar tensors: one copy into the layout the head kernels take)
