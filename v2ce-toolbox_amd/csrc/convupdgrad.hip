@@ -1,0 +1,337 @@
+// convupdgrad.hip -- the input gradients of the last decoder block's first half on gfx950: of the 3x3x3 Conv3d(96, 32) conv1
+// and of the 1x1x1 Conv3d(96, 32) shortcut with respect to the block's two sources, back through the concat and the 2x nearest
+// upsample that the forward never materialises (include/v2ce_hip_convupdgrad.h states the formulas, the tensors and the
+// precision contract).
+//
+// This is convdgrad.hip's kernel, once per 32-channel group of X = cat(upsample(x0), x1).  d_X of a group is a GEMM with the
+// positions as M, the group's 32 input channels as N and (unit, co) as K = 28 x 32: unit u < 27 is tap u of conv1 on g1,
+//   D[pos][ci] += sum_co g1[co][pos - tap + 1] W[co][ci][tap],
+// and unit 27 the shortcut on gd at the position itself.  v_mfma_f32_32x32x2_f32 takes two output channels per instruction:
+// lane l holds A[pos = l & 31][k = l >> 5] and B[k = l >> 5][ci = l & 31].
+//   B  the weights, [group][unit][co][ci] after the prep kernel: wave v keeps those of the units 7 v .. 7 v + 6 in registers
+//      for the whole kernel (the shortcut is the last wave's seventh): 7 x 16 registers per lane
+//   A  sH, the halo of g1 in LDS, channel-major: 3 frames x 4 rows x 66 columns = 792 positions at a plane stride of 800
+//      floats, and sD, gd of the tile, channel-major at a plane stride of 160 floats.  Both strides are 32 mod 64: the 32
+//      lanes of a half read 32 consecutive columns of one row of one channel plane, the other half the next plane, 32 banks
+//      further: one conflict-free ds_read_b32 per MFMA
+//
+// The grid is groups x shares: workgroup G s + c walks share s of the tiles for the c-th requested group (groups 0, 1: the
+// channels 32 c .. of x0, asked for through d_x0; group 2: x1, through d_x1).  A tile is 2 rows x 64 columns of one frame and
+// starts at an even row and an even column, so every 2 x 2 pool of the upsample lies inside one tile: one workgroup produces
+// a d_x0 element whole, with no atomics, whatever the grid.  Per tile the workgroup
+//   1. stages the halo of g1 (zeros outside the frame, the sequence and the row's W columns: the convolution's zero padding)
+//      and the tile of gd, and zero-fills the padding columns of its output rows when the tile is the last one of its rows;
+//   2. runs its units: 4 independent MFMA chains (the tile's four groups of 32 positions) per wave, 7 x 16 steps each;
+//   3. writes the four partial tiles over the halo (sP[wave][position][ci]) and adds them in the order of the waves,
+//      ((p0 + p1) + p2) + p3, per position: group 2 stores that as d_x1; groups 0 and 1 add the up to four positions of a
+//      source pixel in the order (0, 0), (0, 1), (1, 0), (1, 1) -- leaving out those at h >= H or w >= W, which are no output
+//      positions although their convolution sums are not zero -- and store 32 source columns of one source row.
+// An element's order of summation is fixed by the unit split and the pool order alone: it depends neither on the grid nor on
+// the tile walk nor on which other output was asked for.
+#include "common.h"
+
+#include "../../include/v2ce_hip_convupdgrad.h"
+
+namespace v2ce {
+namespace {
+
+constexpr int kThreads = 256;                       // 4 waves
+constexpr int kC = 32;
+constexpr int kCin = 96;
+constexpr int kXGroups = 3;                         // 32-channel groups of X
+constexpr int kTaps = 27;
+constexpr int kUnits = kTaps + 1;                   // the 27 taps of conv1 and the shortcut
+constexpr int kUnitsPerWave = 7;
+constexpr int kSteps = kC / 2;                      // k-steps of a unit: two output channels per MFMA
+constexpr int kTileH = 2, kTileW = 64, kTile = kTileH * kTileW;
+constexpr int kMGroups = kTile / 32;                // M groups of a tile: (row, half of the columns)
+constexpr int kHaloT = 3, kHaloH = kTileH + 2, kHaloW = kTileW + 2;
+constexpr int kHalo = kHaloT * kHaloH * kHaloW;     // 792 positions
+constexpr int kPlane = 800;                         // floats between the channel planes of sH
+constexpr int kPlaneD = 160;                        // floats between the channel planes of sD
+constexpr int kPos = 36;                            // floats between the positions of a partial tile (32 channels + 4: 16-byte rows)
+constexpr int kMaxGrid = 256;                       // one workgroup per CU: 120 KB of LDS each
+constexpr int kWeights = kXGroups * kUnits * kC * kC;
+constexpr size_t kLds = (size_t)kC * (kPlane + kPlaneD) * sizeof(float);
+static_assert(kPlane >= kHalo && kPlane % 64 == 32, "plane stride: the two halves of a wave on disjoint banks");
+static_assert(kPlaneD >= kTile && kPlaneD % 64 == 32, "plane stride of the gd tile");
+static_assert((size_t)4 * kTile * kPos <= (size_t)kC * kPlane && kPos % 4 == 0, "the partial tiles lie over the halo");
+static_assert(kLds <= 160 * 1024, "LDS of one workgroup");
+static_assert(V2CE_UPDGRAD_TERMS == kUnits * kC, "terms of an element of d_X");
+static_assert(kUnits == 4 * kUnitsPerWave, "every wave owns seven units");
+static_assert(kTileH == 2 && kTileW % 2 == 0 && kTileW / 2 * kC / 4 == kThreads, "one thread per four channels of a source pixel");
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct Dims {
+    int B, L, H, W, pitch, H0, W0, pitch0;
+    int tiles_h, tiles_w;
+    long long tiles;                                // B L tiles_h tiles_w
+    size_t total;
+};
+
+// float offset of channel group g of (frame, row, column) in the two-group C16 tensors g1, gd, d_x1
+__device__ __forceinline__ long long c16_at(const Dims &D, long long f, int g, int h, int w) {
+    return ((((f * 2 + g) * D.H + h) * D.pitch) + w) * 16;
+}
+
+// the same in the four-group d_x0, (h0, w0) at the source resolution
+__device__ __forceinline__ long long src_at(const Dims &D, long long f, int g, int h0, int w0) {
+    return ((((f * 4 + g) * D.H0 + h0) * D.pitch0) + w0) * 16;
+}
+
+__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// ((p0 + p1) + p2) + p3 of four channels of a position
+__device__ __forceinline__ float4 wave_sum(const float *src) {
+    float4 s = *reinterpret_cast<const float4 *>(src);
+#pragma unroll
+    for (int v = 1; v < 4; ++v) s = add4(s, *reinterpret_cast<const float4 *>(src + v * kTile * kPos));
+    return s;
+}
+
+// [co][96][27] and [co][96] -> [group][unit][co][ci]: what a lane of the main kernel loads as consecutive floats
+__global__ __launch_bounds__(kThreads) void updgrad_prep_kernel(const float *__restrict__ weight, const float *__restrict__ short_weight,
+                                                                float *__restrict__ wt) {
+    const int e = blockIdx.x * kThreads + threadIdx.x;
+    if (e >= kWeights) return;
+    const int ci = e % kC, co = (e / kC) % kC, unit = (e / (kC * kC)) % kUnits, grp = e / (kUnits * kC * kC);
+    const int at = co * kCin + grp * kC + ci;
+    if (unit < kTaps) {
+        if (weight) wt[e] = weight[at * kTaps + unit];
+    } else if (short_weight) {
+        wt[e] = short_weight[at];
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void updgrad_kernel(const float *__restrict__ wt, const float *__restrict__ g1,
+                                                           const float *__restrict__ gd, Dims D, int grp0, int ngrp,
+                                                           float *__restrict__ d_x0, float *__restrict__ d_x1) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *sH = smem, *sD = smem + kC * kPlane, *sP = smem;     // the partial tiles lie over the halo once it has been read
+    const int t = threadIdx.x, lane = t & (kWave - 1);
+    const int wv = __builtin_amdgcn_readfirstlane(t / kWave);
+    const int grp = grp0 + (int)(blockIdx.x % ngrp);
+    const long long share = blockIdx.x / ngrp, shares = gridDim.x / ngrp;
+    const long long t0 = share * D.tiles / shares, t1 = (share + 1) * D.tiles / shares;
+    const bool doC = g1 != nullptr, doS = gd != nullptr;
+    const bool short_wave = wv == kUnits / kUnitsPerWave - 1;
+
+    // B operands of this wave's units: step s of unit u is W[co = 2 s + (lane >> 5)][ci = 32 grp + (lane & 31)][u]
+    float wreg[kUnitsPerWave][kSteps];
+    int tapoff[kUnitsPerWave];                      // the tap's shift inside a plane of sH: g1 at pos - tap + 1
+#pragma unroll
+    for (int j = 0; j < kUnitsPerWave; ++j) {
+        const int unit = wv * kUnitsPerWave + j, kt = unit / 9, kh = (unit / 3) % 3, kw = unit % 3;
+        const bool live = unit < kTaps ? doC : doS;
+        tapoff[j] = unit < kTaps ? ((2 - kt) * kHaloH + (2 - kh)) * kHaloW + (2 - kw) : 0;
+#pragma unroll
+        for (int s = 0; s < kSteps; ++s)
+            wreg[j][s] = live ? wt[((grp * kUnits + unit) * kC + 2 * s + (lane >> 5)) * kC + (lane & 31)] : 0.0f;
+    }
+
+    for (long long tile = t0; tile < t1; ++tile) {
+        const int tw = (int)(tile % D.tiles_w);
+        const long long r1 = tile / D.tiles_w;
+        const int th = (int)(r1 % D.tiles_h);
+        const long long f = r1 / D.tiles_h;          // frame b L + l
+        const int l = (int)(f % D.L), h0 = th * kTileH, w0 = tw * kTileW;
+
+        __syncthreads();                             // the previous tile's partials have been read
+        if (doC) {
+            // the halo of g1: 2 channel groups x 792 positions, 64 bytes each; consecutive lanes take consecutive positions
+            for (int i = t; i < 2 * kHalo; i += kThreads) {
+                const int g = i / kHalo, hp = i % kHalo;
+                const int dt = hp / (kHaloH * kHaloW), rem = hp % (kHaloH * kHaloW), hh = rem / kHaloW, ww = rem % kHaloW;
+                const int ll = l + dt - 1, h = h0 + hh - 1, w = w0 + ww - 1;
+                float4 v[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (ll >= 0 && ll < D.L && h >= 0 && h < D.H && w >= 0 && w < D.W) {
+                    const long long at = c16_at(D, f + dt - 1, g, h, w);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float4 *>(g1 + at + q * 4);
+                }
+                float *dst = sH + (g * 16) * kPlane + hp;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    dst[(q * 4 + 0) * kPlane] = v[q].x; dst[(q * 4 + 1) * kPlane] = v[q].y;
+                    dst[(q * 4 + 2) * kPlane] = v[q].z; dst[(q * 4 + 3) * kPlane] = v[q].w;
+                }
+            }
+        }
+        if (doS) {
+            // gd of the tile: 2 channel groups x 128 positions, one per thread
+            const int g = t / kTile, p = t % kTile;
+            const int h = h0 + p / kTileW, w = w0 + p % kTileW;
+            float4 v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (h < D.H && w < D.W) {
+                const long long at = c16_at(D, f, g, h, w);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float4 *>(gd + at + q * 4);
+            }
+            float *dst = sD + (g * 16) * kPlaneD + p;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                dst[(q * 4 + 0) * kPlaneD] = v[q].x; dst[(q * 4 + 1) * kPlaneD] = v[q].y;
+                dst[(q * 4 + 2) * kPlaneD] = v[q].z; dst[(q * 4 + 3) * kPlaneD] = v[q].w;
+            }
+        }
+        if (tw == D.tiles_w - 1) {
+            // the padding columns of the tile's output rows: (row, group of 16, column, piece of 16 bytes)
+            const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (grp == 2) {
+                const int pad = D.pitch - D.W;
+                const long long n = (long long)kTileH * 2 * pad * 4;
+                for (long long i = t; i < n; i += kThreads) {
+                    const int piece = (int)(i & 3), col = (int)((i >> 2) % pad), rg = (int)((i >> 2) / pad), g = rg & 1, h = h0 + (rg >> 1);
+                    if (h >= D.H) continue;
+                    *reinterpret_cast<float4 *>(d_x1 + c16_at(D, f, g, h, D.W + col) + piece * 4) = zero;
+                }
+            } else {
+                const int pad = D.pitch0 - D.W0;
+                const long long n = (long long)2 * pad * 4;
+                for (long long i = t; i < n; i += kThreads) {
+                    const int piece = (int)(i & 3), col = (int)((i >> 2) % pad), g = (int)((i >> 2) / pad);
+                    *reinterpret_cast<float4 *>(d_x0 + src_at(D, f, grp * 2 + g, h0 >> 1, D.W0 + col) + piece * 4) = zero;
+                }
+            }
+        }
+        __syncthreads();
+
+        f32x16 acc[kMGroups];
+#pragma unroll
+        for (int gq = 0; gq < kMGroups; ++gq)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[gq][r] = 0.0f;
+        // group gq = (row gq >> 1, columns 32 (gq & 1) ..): lane's position inside a plane before the tap's shift
+        const float *a0 = sH + (lane >> 5) * kPlane + (lane & 31);
+        const float *d0 = sD + (lane >> 5) * kPlaneD + (lane & 31);
+#pragma unroll
+        for (int j = 0; j < kUnitsPerWave; ++j) {
+            if (j == kUnitsPerWave - 1 && short_wave) {
+                if (doS) {
+#pragma unroll
+                    for (int s = 0; s < kSteps; ++s) {
+#pragma unroll
+                        for (int gq = 0; gq < kMGroups; ++gq) {
+                            const float a = d0[2 * s * kPlaneD + gq * 32];
+                            acc[gq] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wreg[j][s], acc[gq], 0, 0, 0);
+                        }
+                    }
+                }
+            } else if (doC) {
+                const float *aj = a0 + tapoff[j];
+#pragma unroll
+                for (int s = 0; s < kSteps; ++s) {
+#pragma unroll
+                    for (int gq = 0; gq < kMGroups; ++gq) {
+                        const float a = aj[2 * s * kPlane + (gq >> 1) * kHaloW + (gq & 1) * 32];
+                        acc[gq] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wreg[j][s], acc[gq], 0, 0, 0);
+                    }
+                }
+            }
+        }
+        __syncthreads();                             // every wave has read the halo
+
+        // C/D map of the 32x32 MFMA: column (ci) = lane & 31, row (position) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+#pragma unroll
+        for (int gq = 0; gq < kMGroups; ++gq) {
+            float *blk = sP + ((size_t)wv * kTile + gq * 32) * kPos + (lane & 31);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) blk[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * kPos] = acc[gq][r];
+        }
+        __syncthreads();
+
+        if (grp == 2) {
+            // position p = row * 64 + column of the tile; 8 pieces of four channels each
+#pragma unroll
+            for (int k = 0; k < kTile * 8 / kThreads; ++k) {
+                const int i = t + k * kThreads, piece = i & 3, rest = i >> 2, p = rest % kTile, g = rest / kTile;
+                const int h = h0 + p / kTileW, w = w0 + p % kTileW;
+                if (h < D.H && w < D.W)
+                    *reinterpret_cast<float4 *>(d_x1 + c16_at(D, f, g, h, w) + piece * 4) = wave_sum(sP + p * kPos + g * 16 + piece * 4);
+            }
+        } else {
+            // source pixel (h0 / 2, w0 / 2 + col): its output positions are rows h0, h0 + 1 and columns w0 + 2 col, + 1
+            const int piece = t & 3, col = (t >> 2) & 31, g = t >> 7;
+            const int w = w0 + 2 * col;
+            if (w < D.W) {
+                const float *src = sP + 2 * col * kPos + g * 16 + piece * 4;
+                const bool right = w + 1 < D.W, below = h0 + 1 < D.H;
+                float4 s = wave_sum(src);
+                if (right) s = add4(s, wave_sum(src + kPos));
+                if (below) s = add4(s, wave_sum(src + kTileW * kPos));
+                if (below && right) s = add4(s, wave_sum(src + (kTileW + 1) * kPos));
+                *reinterpret_cast<float4 *>(d_x0 + src_at(D, f, grp * 2 + g, h0 >> 1, (w0 >> 1) + col) + piece * 4) = s;
+            }
+        }
+    }
+}
+
+bool make_dims(int B, int L, int H, int W, int pitch, int pitch0, int max_workgroups, Dims &D) {
+    if (B < 1 || L < 1 || H < 1 || W < 1 || pitch < W || max_workgroups < 0) return false;
+    const int H0 = (H - 1) / 2 + 1, W0 = (W - 1) / 2 + 1;
+    if (pitch0 < W0) return false;
+    const long long N = (long long)B * L * H * W;
+    if ((long long)B * L >= (1ll << 31) || (long long)H * W >= (1ll << 31) || N >= (1ll << 31)) return false;
+    if ((long long)B * L * H >= (1ll << 34) || (long long)B * L * H * pitch >= (1ll << 34)) return false;
+    if ((long long)B * L * H0 * pitch0 >= (1ll << 34)) return false;
+    D.B = B; D.L = L; D.H = H; D.W = W; D.pitch = pitch; D.H0 = H0; D.W0 = W0; D.pitch0 = pitch0;
+    D.tiles_h = (H + kTileH - 1) / kTileH;
+    D.tiles_w = (W + kTileW - 1) / kTileW;
+    D.tiles = (long long)B * L * D.tiles_h * D.tiles_w;
+    D.total = ((size_t)kWeights * sizeof(float) + 255) & ~(size_t)255;     // the repacked weights; the grid needs nothing
+    return true;
+}
+
+const char *kNeeds = "needs B, L, H, W >= 1, pitch >= W, pitch0 >= (W + 1) / 2, max_workgroups >= 0, B L H W < 2^31, B L H pitch "
+                     "< 2^34 and B L H0 pitch0 < 2^34";
+
+}  // namespace
+}  // namespace v2ce
+
+using namespace v2ce;
+
+extern "C" size_t v2ce_convup_dgrad_workspace_bytes(int B, int L, int H, int W, int pitch, int pitch0, int max_workgroups) {
+    Dims D;
+    return make_dims(B, L, H, W, pitch, pitch0, max_workgroups, D) ? D.total : 0;
+}
+
+extern "C" int v2ce_convup_dgrad(const float *weight, const float *short_weight, const float *g1, const float *gd, int B, int L,
+                                 int H, int W, int pitch, int pitch0, float *d_x0, float *d_x1, void *workspace,
+                                 size_t workspace_bytes, int max_workgroups, v2ce_stream_t stream) {
+    clear_error();
+    Dims D;
+    V2CE_REQUIRE(make_dims(B, L, H, W, pitch, pitch0, max_workgroups, D), V2CE_ERR_BAD_ARG,
+                 "v2ce_convup_dgrad: B %d L %d H %d W %d pitch %d pitch0 %d max_workgroups %d: %s", B, L, H, W, pitch, pitch0,
+                 max_workgroups, kNeeds);
+    V2CE_REQUIRE(d_x0 || d_x1, V2CE_ERR_BAD_ARG, "v2ce_convup_dgrad: no output requested (d_x0 and d_x1 are both null)");
+    V2CE_REQUIRE(workspace && (g1 || gd) && (!g1 || weight) && (!gd || short_weight), V2CE_ERR_BAD_ARG,
+                 "v2ce_convup_dgrad: null pointer (g1 and gd are both null, g1 without weight, gd without short_weight, or no "
+                 "workspace)");
+    V2CE_REQUIRE(aligned16(g1, gd, d_x0, d_x1), V2CE_ERR_BAD_ARG, "v2ce_convup_dgrad: g1, gd, d_x0 and d_x1 must be 16-byte aligned");
+    V2CE_REQUIRE(((reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(short_weight)) & 3) == 0, V2CE_ERR_BAD_ARG,
+                 "v2ce_convup_dgrad: weight and short_weight must be 4-byte aligned");
+    V2CE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, V2CE_ERR_BAD_ARG,
+                 "v2ce_convup_dgrad: workspace must be 8-byte aligned");
+    V2CE_REQUIRE(workspace_bytes >= D.total, V2CE_ERR_WORKSPACE, "v2ce_convup_dgrad: workspace too small (%zu < %zu)",
+                 workspace_bytes, D.total);
+    // the requested 32-channel groups of X: 0, 1 (d_x0) and 2 (d_x1)
+    const int grp0 = d_x0 ? 0 : 2, ngrp = (d_x0 ? 2 : 0) + (d_x1 ? 1 : 0);
+    long long shares = D.tiles < kMaxGrid / ngrp ? D.tiles : kMaxGrid / ngrp;
+    const long long cap = max_workgroups / ngrp > 0 ? max_workgroups / ngrp : 1;
+    if (max_workgroups > 0 && shares > cap) shares = cap;
+    hipStream_t st = as_stream(stream);
+    float *wt = static_cast<float *>(workspace);
+    V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(updgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)kLds));
+    hipLaunchKernelGGL(updgrad_prep_kernel, dim3((kWeights + kThreads - 1) / kThreads), dim3(kThreads), 0, st, g1 ? weight : nullptr,
+                       gd ? short_weight : nullptr, wt);
+    hipLaunchKernelGGL(updgrad_kernel, dim3((unsigned)(shares * ngrp)), dim3(kThreads), kLds, st, wt, g1, gd, D, grp0, ngrp, d_x0,
+                       d_x1);
+    V2CE_HIP_CHECK(hipGetLastError());
+    return V2CE_OK;
+}

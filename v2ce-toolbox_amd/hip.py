@@ -65,6 +65,10 @@ DGRAD_TERMS = 864                        # V2CE_DGRAD_TERMS: f32 terms of one d_
 CONVUPGRAD_EXPORTS = ("v2ce_convup_wgrad_workspace_bytes", "v2ce_convup_wgrad")
 UPWGRAD_CHAIN = 4096                     # V2CE_UPWGRAD_CHAIN: positions one f32 accumulator sums before it meets the f64 sum
 
+# the input gradients of the same two layers, back through the concat and the upsample (include/v2ce_hip_convupdgrad.h)
+CONVUPDGRAD_EXPORTS = ("v2ce_convup_dgrad_workspace_bytes", "v2ce_convup_dgrad")
+UPDGRAD_TERMS = 896                      # V2CE_UPDGRAD_TERMS: f32 terms of one d_X element (32 output channels x 28 units)
+
 
 LAYOUT_PLANAR, LAYOUT_C16 = 0, 1
 
@@ -326,6 +330,10 @@ def lib() -> ctypes.CDLL:
     L.v2ce_convup_wgrad_workspace_bytes.restype = sz
     L.v2ce_convup_wgrad.argtypes = [vp, vp, vp, vp] + [i32] * 6 + [vp, vp, vp, vp, sz, i32, vp]
     L.v2ce_convup_wgrad.restype = ctypes.c_int
+    L.v2ce_convup_dgrad_workspace_bytes.argtypes = [i32] * 7
+    L.v2ce_convup_dgrad_workspace_bytes.restype = sz
+    L.v2ce_convup_dgrad.argtypes = [vp, vp, vp, vp] + [i32] * 6 + [vp, vp, vp, sz, i32, vp]
+    L.v2ce_convup_dgrad.restype = ctypes.c_int
     L.v2ce_voxelize_batch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
     L.v2ce_voxelize_batch_workspace_bytes.restype = sz
     L.v2ce_voxelize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
