@@ -329,6 +329,93 @@ def fit_last_block(model, image_units, gt_voxels, *, train: Sequence[str] = LAST
     return history
 
 
+DEC2_CONV_GROUPS = LAST_BLOCK_GROUPS + ("dec2_conv2", "dec2_bn2")
+
+
+def fit_dec2_conv(model, image_units, gt_voxels, *, train: Sequence[str] = DEC2_CONV_GROUPS,
+                  loss: Sequence[str] = losses.DEFAULT_LOSS, steps: int, lr: float, optimizer: str = "adam",
+                  cache_bytes: int = DEFAULT_CACHE_BYTES, **loss_options) -> List[dict]:
+    """Fit the last decoder block, ``UNet.pred`` and the layer in front of them: what ``fit_last_block`` trains, and the
+    second convolution of ``UNet.decoders[2]`` -- the spectral-normalised 3x3x3 ``Conv3d(64, 64)`` that produces the last
+    block's source -- with its ``bn2``, whose gradients arrive through the last block's upsample (``v2ce_convup_dgrad``) and
+    are formed by ``v2ce_convn_wgrad``.
+
+    ``train`` names the parameter groups one optimizer steps: those of ``fit_last_block``, 'dec2_conv2' (the
+    convolution's ``weight_bar``) and 'dec2_bn2' (the BatchNorm's weight and bias; its statistics stay frozen).  The
+    other arguments and the returned history are those of ``fit_last_block``.  With neither 'dec2_conv2' nor 'dec2_bn2' in
+    ``train`` this is ``fit_last_block`` with the same arguments, step for step.
+
+    The two inputs of the convolution and the last block's skip tensor (``V2ce3d.forward_dec2_inputs``) are computed once
+    per window and kept while the kept ones fit in ``cache_bytes``; every step is ``Dec2Conv`` -> ``LastBlock`` ->
+    ``PredHead`` -> ``losses.calculate_loss`` -> ``backward()`` -> one optimizer step.  The last block is asked for the
+    gradient of its source alone: the skip tensor requires none.  As in the reference, every forward of a trained
+    convolution advances its spectral-norm u / v by one power iteration.
+
+    On return the model differs from its state on entry in the trained tensors and in the ``weight_u`` / ``weight_v`` of
+    dec2's conv2 and of the last block's conv1 and conv2, which keep the iterations the fit applied; the other nine
+    spectral-norm layers and the call counter are restored."""
+    from .dec2_conv import Dec2Conv
+    from .last_block import LastBlock
+    train = tuple(train)
+    if not train or any(g not in DEC2_CONV_GROUPS for g in train) or len(set(train)) != len(train):
+        raise ValueError(f"train must be a non-empty subset of {DEC2_CONV_GROUPS}, got {train}")
+    if not ("dec2_conv2" in train or "dec2_bn2" in train):
+        return fit_last_block(model, image_units, gt_voxels, train=train, loss=loss, steps=steps, lr=lr, optimizer=optimizer,
+                              cache_bytes=cache_bytes, **loss_options)
+    loss = losses.check_loss_names(loss)
+    if optimizer not in ("adam", "sgd"):
+        raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
+    if int(steps) < 0:
+        raise ValueError(f"steps must be >= 0, got {steps}")
+    windows = _windows(image_units, gt_voxels)
+    head, block, dec2 = PredHead.from_model(model), LastBlock.from_model(model), Dec2Conv.from_model(model)
+    convs, norms, conv = block.convs, block.norms, block.conv
+    groups = {"pred": [head.weight, head.bias], "conv2": [conv.weight_bar], "bn2": [conv.bn_weight, conv.bn_bias],
+              "bn1": [norms.bn1_weight, norms.bn1_bias], "bnd": [norms.bnd_weight, norms.bnd_bias],
+              "conv1": [convs.weight_bar],
+              "convd": [convs.short_weight] + ([convs.short_bias] if convs.short_bias is not None else []),
+              "dec2_conv2": [dec2.weight_bar], "dec2_bn2": [dec2.bn_weight, dec2.bn_bias]}
+    for g, ps in groups.items():
+        for p in ps:
+            p.requires_grad_(g in train)
+    opt = (torch.optim.Adam if optimizer == "adam" else torch.optim.SGD)([p for g in train for p in groups[g]], lr=lr)
+    snap = model.sn_snapshot()
+    cache, used = {}, 0
+
+    def inputs(i):
+        nonlocal used
+        if i in cache:
+            return cache[i]
+        model.sn_restore(snap)
+        trio = model.forward_dec2_inputs(windows[i][0])
+        nb = sum(a.numel() for a in trio) * 4
+        if used + nb <= cache_bytes:
+            cache[i], used = trio, used + nb
+        return trio
+
+    history = []
+    try:
+        for k in range(int(steps)):
+            i = k % len(windows)
+            opt.zero_grad(set_to_none=True)
+            t2, res2, x1 = inputs(i)
+            pred = head(block(dec2(t2, res2), x1))
+            total, d = losses.calculate_loss(pred, windows[i][1].contiguous(), loss=loss, **loss_options)
+            total.backward()
+            opt.step()
+            history.append({"loss": float(total.detach()), "loss_dict": {n: float(v) for n, v in d.items()}})
+    finally:
+        model.sn_restore(snap)
+    bound = max(float(conv.guard), float(convs.guard), float(dec2.guard))
+    if model.precision == "f16x2" and bound > model.RANGE_GUARD_LIMIT:
+        logger.warning(f"split-half range guard of the trained convolutions: bound {bound:.3e} > "
+                       f"{model.RANGE_GUARD_LIMIT:.1e}; fit with precision='f32'")
+    head.write_back(model)
+    block.write_back(model)
+    dec2.write_back(model)
+    return history
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # command line
 
@@ -363,11 +450,12 @@ def build_parser():
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--optimizer", default="adam", choices=("adam", "sgd"))
-    p.add_argument("--train", default="head", choices=("head", "tail", "tail_norms", "last_block"),
+    p.add_argument("--train", default="head", choices=("head", "tail", "tail_norms", "last_block", "dec2_conv2"),
                    help="head: UNet.pred alone (fit_head); tail: the last decoder convolution, its bn2 and UNet.pred (fit_tail); "
                         "tail_norms: those and the last decoder block's bn1 and downsample.1 (fit_tail_norms); "
                         "last_block: those and the block's conv1 and shortcut convolution, the whole last decoder block "
-                        "(fit_last_block)")
+                        "(fit_last_block); dec2_conv2: those and the second convolution of the decoder in front, UNet.decoders[2].conv2 "
+                        "with its bn2 (fit_dec2_conv)")
     p.add_argument("--cache_gb", type=float, default=DEFAULT_CACHE_BYTES / 2 ** 30, help="feature cache budget")
     p.add_argument("-o", "--out", type=str, default="./tuned.pt", help="the tuned state_dict (v2ce.py -m loads it)")
     p.add_argument("--history", type=str, default=None, help="the per-step history as JSON (default: <out>.history.json)")
@@ -435,7 +523,8 @@ def main(argv=None):
     names = tuple(args.losses) if args.losses else losses.DEFAULT_LOSS
     opts = {k: getattr(args, k) for k in ("ef_type", "add_base_loss", "alpha_pyramid", "alpha_ef", "alpha_efc",
                                           "alpha_match", "alpha_compensation", "alpha_pt", "alpha_norm")}
-    fit = {"head": fit_head, "tail": fit_tail, "tail_norms": fit_tail_norms, "last_block": fit_last_block}[args.train]
+    fit = {"head": fit_head, "tail": fit_tail, "tail_norms": fit_tail_norms, "last_block": fit_last_block,
+           "dec2_conv2": fit_dec2_conv}[args.train]
     history = fit(model, xs, gs, loss=names, steps=args.steps, lr=args.lr, optimizer=args.optimizer,
                   cache_bytes=int(args.cache_gb * 2 ** 30), **opts)
     os.makedirs(op.dirname(op.abspath(args.out)), exist_ok=True)

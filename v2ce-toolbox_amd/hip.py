@@ -69,6 +69,12 @@ UPWGRAD_CHAIN = 4096                     # V2CE_UPWGRAD_CHAIN: positions one f32
 CONVUPDGRAD_EXPORTS = ("v2ce_convup_dgrad_workspace_bytes", "v2ce_convup_dgrad")
 UPDGRAD_TERMS = 896                      # V2CE_UPDGRAD_TERMS: f32 terms of one d_X element (32 output channels x 28 units)
 
+# the weight and input gradients of a 3x3x3 convolution with 32 or 64 channels on either side: UNet.decoders[2].conv2
+# (include/v2ce_hip_convngrad.h)
+CONVNGRAD_EXPORTS = ("v2ce_convn_wgrad_workspace_bytes", "v2ce_convn_wgrad", "v2ce_convn_dgrad_workspace_bytes",
+                     "v2ce_convn_dgrad")
+CONVN_CHANNELS = (32, 64)                # what cin and cout may be
+
 
 LAYOUT_PLANAR, LAYOUT_C16 = 0, 1
 
@@ -334,6 +340,14 @@ def lib() -> ctypes.CDLL:
     L.v2ce_convup_dgrad_workspace_bytes.restype = sz
     L.v2ce_convup_dgrad.argtypes = [vp, vp, vp, vp] + [i32] * 6 + [vp, vp, vp, sz, i32, vp]
     L.v2ce_convup_dgrad.restype = ctypes.c_int
+    L.v2ce_convn_wgrad_workspace_bytes.argtypes = [i32] * 8
+    L.v2ce_convn_wgrad_workspace_bytes.restype = sz
+    L.v2ce_convn_wgrad.argtypes = [vp, vp, vp] + [i32] * 7 + [vp, vp, vp, sz, i32, vp]
+    L.v2ce_convn_wgrad.restype = ctypes.c_int
+    L.v2ce_convn_dgrad_workspace_bytes.argtypes = [i32] * 8
+    L.v2ce_convn_dgrad_workspace_bytes.restype = sz
+    L.v2ce_convn_dgrad.argtypes = [vp, vp, vp] + [i32] * 7 + [vp, vp, vp, sz, i32, vp]
+    L.v2ce_convn_dgrad.restype = ctypes.c_int
     L.v2ce_voxelize_batch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
     L.v2ce_voxelize_batch_workspace_bytes.restype = sz
     L.v2ce_voxelize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]

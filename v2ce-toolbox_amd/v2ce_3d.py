@@ -800,6 +800,23 @@ class V2ce3d(nn.Module):
                          split=self._split(blk.cin, blk.cout, 1, s))
         return t, res
 
+    def _block_inputs_unfused(self, blk: _ResidualBlock3D, d, x0, x1=None, up_to=None):
+        """(relu(bn1(conv1 x)), bn_d(conv_d x)) of a block whose shortcut normally rides in conv2's K loop (``_fold_shortcut``)
+        or has a launch of its own: conv1 as ``_block`` launches it in front of such a conv2, and the shortcut's own 1x1x1
+        launch of ``_block``'s last branch (``down_w`` and ``down_bn`` are prepared for every block)."""
+        assert not self._fuse_shortcut(blk), "the block's shortcut rides on conv1's launch: _block_inputs returns its pair"
+        s = blk.stride_hw
+        w1, bn1 = d["conv1_w"], d.get("bn1_eff", d["bn1"])
+        if d.get("conv1_skip_w") is not None and x1 is not None and self._up2_ok(x0, x1, w1, up_to):
+            part = self._conv_up_part(x0, x1, w1, *bn1, blk.cout, up_to)
+            t = self._conv(x1, None, d["conv1_skip_w"], bn1[0], d["zero_shift"], blk.cout, 3, 1, hip.ACT_RELU, residual=part,
+                           split=True)
+        else:
+            t = self._conv(x0, x1, w1, *bn1, blk.cout, 3, s, hip.ACT_RELU, up_to=up_to, split=self._split(blk.cin, blk.cout))
+        res = self._conv(x0, x1, d["down_w"], *d["down_bn"], blk.cout, 1, s, hip.ACT_NONE, up_to=up_to,
+                         split=self._split(blk.cin, blk.cout, 1, s))
+        return t, res
+
     def _normed_epilogues(self, blk, d):
         """-> ((scale1, shift1), (scale_d, shift_d)): the epilogue vectors with which conv1's launch gives (conv1(.) / sigma -
         mean1) rsqrt(var1 + eps) and the shortcut's gives (conv_d(.) + bias_d - mean_d) rsqrt(var_d + eps).  They are built
@@ -931,6 +948,22 @@ class V2ce3d(nn.Module):
                 a.absmax = a.absmax.clone()
         return x0, x1
 
+    @torch.no_grad()
+    def forward_dec2_inputs(self, x: torch.Tensor):
+        """x [B,L,2,H,W] -> (t2, res2, x1): the two tensors the conv2 launch of the decoder in front of the last one
+        (``UNet.decoders[2]``) reads -- t2 = relu(bn1(conv1(.))), its input, and res2 = bn_d(conv_d(.)), that block's shortcut
+        branch, both 64 channels at half the resolution, [B,L,4,H0,pitch0,16] -- and x1, the last decoder block's skip tensor
+        (32 channels, [B,L,2,H,pitch,16]); all channels-last-16 with the logical width in ``.lw``, without gradient
+        (dec2_conv.py: ``Dec2Conv`` turns the pair into ``forward_tail_sources``'s x0).  In ``f16x2`` that block's shortcut
+        normally rides in conv2's K loop and res2 never exists: this accessor makes conv1's launch and the shortcut's own
+        1x1x1 launch instead.  Everything in front of the block runs exactly as in ``forward_tail_sources`` -- the same
+        spectral-norm power iteration (one per call, every layer's included), range-guard policy and precision."""
+        out = self._guarded_forward(x, False, features="dec2")
+        for a in out:                   # the range slots are views of a table the next call clears: keep this call's values
+            if hasattr(a, "absmax"):
+                a.absmax = a.absmax.clone()
+        return out
+
     def _guarded_forward(self, x, return_intermediates, features=False):
         if x.dim() != 5 or x.shape[2] != self.in_channels:
             raise ValueError(f"expected x of shape [B,L,{self.in_channels},H,W], got {tuple(x.shape)}")
@@ -961,7 +994,8 @@ class V2ce3d(nn.Module):
         """features=True: stop in front of UNet.pred and return its input (forward_features); features="tail": stop in front
         of the last decoder block's conv2 and return its two inputs (forward_tail_inputs); features="normed": the same two launches
         without the BatchNorms' affine parts and the relu (forward_tail_normed); features="sources": stop in front of the last decoder
-        block and return the two tensors it reads (forward_tail_sources); the default launches are today's."""
+        block and return the two tensors it reads (forward_tail_sources); features="dec2": stop in front of conv2 of the decoder before
+        it and return that launch's two inputs and the last block's skip tensor (forward_dec2_inputs); the default launches are today's."""
         if self._prep is None:
             self._prepare()
         P, U = self._prep, self.UNet
@@ -996,6 +1030,10 @@ class V2ce3d(nn.Module):
         fuse = P["pred_fused"] if not (return_intermediates or features) else None
         for i, (blk, skip) in enumerate(zip(U.decoders, reversed(skips))):       # :357-365
             last = i == len(U.decoders) - 1
+            if features == "dec2" and i == len(U.decoders) - 2:
+                nxt = list(reversed(skips))[i + 1]
+                h = self._block_inputs_unfused(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4]))) + (nxt,)
+                break
             if last and features == "sources":
                 h = (h, skip)
                 break
@@ -1006,7 +1044,7 @@ class V2ce3d(nn.Module):
             h = self._block(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])),
                             pred=fuse if last else None)
             inter[f"dec{i}"] = self.to_planar(h) if return_intermediates else None
-        if features in ("tail", "normed", "sources"):
+        if features in ("tail", "normed", "sources", "dec2"):
             out = tuple(a if getattr(a, "c16", False) else self.to_c16(a) for a in h)
         elif features:
             # (the exact-f32 kernels produce planar tensors: one copy into the layout the head kernels take)
