@@ -75,6 +75,11 @@ CONVNGRAD_EXPORTS = ("v2ce_convn_wgrad_workspace_bytes", "v2ce_convn_wgrad", "v2
                      "v2ce_convn_dgrad")
 CONVN_CHANNELS = (32, 64)                # what cin and cout may be
 
+# the weight gradients of a decoder block's conv1 and shortcut on the upsample + concat input with the channel counts as
+# arguments: UNet.decoders[2].conv1 and .downsample[0] (include/v2ce_hip_convupngrad.h)
+CONVUPNGRAD_EXPORTS = ("v2ce_convupn_wgrad_workspace_bytes", "v2ce_convupn_wgrad")
+CONVUPN_C0, CONVUPN_C1, CONVUPN_COUT = (64, 128), (32, 64), (32, 64)     # what c0, c1 and cout may be
+
 
 LAYOUT_PLANAR, LAYOUT_C16 = 0, 1
 
@@ -348,6 +353,10 @@ def lib() -> ctypes.CDLL:
     L.v2ce_convn_dgrad_workspace_bytes.restype = sz
     L.v2ce_convn_dgrad.argtypes = [vp, vp, vp] + [i32] * 7 + [vp, vp, vp, sz, i32, vp]
     L.v2ce_convn_dgrad.restype = ctypes.c_int
+    L.v2ce_convupn_wgrad_workspace_bytes.argtypes = [i32] * 10
+    L.v2ce_convupn_wgrad_workspace_bytes.restype = sz
+    L.v2ce_convupn_wgrad.argtypes = [vp, vp, vp, vp] + [i32] * 9 + [vp, vp, vp, vp, sz, i32, vp]
+    L.v2ce_convupn_wgrad.restype = ctypes.c_int
     L.v2ce_voxelize_batch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
     L.v2ce_voxelize_batch_workspace_bytes.restype = sz
     L.v2ce_voxelize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]

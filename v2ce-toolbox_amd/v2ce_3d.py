@@ -800,20 +800,25 @@ class V2ce3d(nn.Module):
                          split=self._split(blk.cin, blk.cout, 1, s))
         return t, res
 
-    def _block_inputs_unfused(self, blk: _ResidualBlock3D, d, x0, x1=None, up_to=None):
+    def _block_inputs_unfused(self, blk: _ResidualBlock3D, d, x0, x1=None, up_to=None, normed=False):
         """(relu(bn1(conv1 x)), bn_d(conv_d x)) of a block whose shortcut normally rides in conv2's K loop (``_fold_shortcut``)
         or has a launch of its own: conv1 as ``_block`` launches it in front of such a conv2, and the shortcut's own 1x1x1
-        launch of ``_block``'s last branch (``down_w`` and ``down_bn`` are prepared for every block)."""
+        launch of ``_block``'s last branch (``down_w`` and ``down_bn`` are prepared for every block).  ``normed``: the same
+        launches without activation and with epilogue vectors that leave the two BatchNorms' affine parts out
+        (``_normed_epilogues``): the normalised, pre-affine pair (z1, zd) of ``forward_dec2_normed``."""
         assert not self._fuse_shortcut(blk), "the block's shortcut rides on conv1's launch: _block_inputs returns its pair"
         s = blk.stride_hw
-        w1, bn1 = d["conv1_w"], d.get("bn1_eff", d["bn1"])
+        w1, bn1, down_bn, act = d["conv1_w"], d.get("bn1_eff", d["bn1"]), d["down_bn"], hip.ACT_RELU
+        if normed:
+            bn1, down_bn = self._normed_epilogues(blk, d)
+            act = hip.ACT_NONE
         if d.get("conv1_skip_w") is not None and x1 is not None and self._up2_ok(x0, x1, w1, up_to):
             part = self._conv_up_part(x0, x1, w1, *bn1, blk.cout, up_to)
-            t = self._conv(x1, None, d["conv1_skip_w"], bn1[0], d["zero_shift"], blk.cout, 3, 1, hip.ACT_RELU, residual=part,
+            t = self._conv(x1, None, d["conv1_skip_w"], bn1[0], d["zero_shift"], blk.cout, 3, 1, act, residual=part,
                            split=True)
         else:
-            t = self._conv(x0, x1, w1, *bn1, blk.cout, 3, s, hip.ACT_RELU, up_to=up_to, split=self._split(blk.cin, blk.cout))
-        res = self._conv(x0, x1, d["down_w"], *d["down_bn"], blk.cout, 1, s, hip.ACT_NONE, up_to=up_to,
+            t = self._conv(x0, x1, w1, *bn1, blk.cout, 3, s, act, up_to=up_to, split=self._split(blk.cin, blk.cout))
+        res = self._conv(x0, x1, d["down_w"], *down_bn, blk.cout, 1, s, hip.ACT_NONE, up_to=up_to,
                          split=self._split(blk.cin, blk.cout, 1, s))
         return t, res
 
@@ -964,6 +969,36 @@ class V2ce3d(nn.Module):
                 a.absmax = a.absmax.clone()
         return out
 
+    @torch.no_grad()
+    def forward_dec2_sources(self, x: torch.Tensor):
+        """x [B,L,2,H,W] -> (h1, s2, x1): the two tensors the decoder in front of the last one (``UNet.decoders[2]``) reads --
+        h1, the output of ``UNet.decoders[1]`` (128 channels at a quarter of the resolution, [B,L,8,H00,pitch00,16]), which the
+        block upsamples, and s2, its skip tensor (64 channels at half the resolution, [B,L,4,H0,pitch0,16]) -- and x1, the last
+        decoder block's skip tensor (32 channels, [B,L,2,H,pitch,16]); all channels-last-16 with the logical width in ``.lw``,
+        without gradient (dec2_block.py: ``Dec2Convs`` turns the first two into ``forward_dec2_normed``'s pair).  Everything
+        in front of the block runs exactly as in ``forward_dec2_inputs`` -- the same spectral-norm power iteration (one per
+        call, every layer's included), range-guard policy and precision -- and stops in front of the block."""
+        out = self._guarded_forward(x, False, features="dec2_sources")
+        for a in out:                   # the range slots are views of a table the next call clears: keep this call's values
+            if hasattr(a, "absmax"):
+                a.absmax = a.absmax.clone()
+        return out
+
+    @torch.no_grad()
+    def forward_dec2_normed(self, x: torch.Tensor):
+        """x [B,L,2,H,W] -> (z1, zd, x1): the normalised, pre-affine outputs of the first half of ``UNet.decoders[2]`` -- z1 =
+        (conv1(.) / sigma - mean1) rsqrt(var1 + eps) and zd = (conv_d(.) + bias_d - mean_d) rsqrt(var_d + eps), both 64
+        channels at half the resolution, [B,L,4,H0,pitch0,16] -- and x1, the last decoder block's skip tensor; all
+        channels-last-16 with the logical width in ``.lw``, without gradient (dec2_block.py: ``Dec2Norms`` turns the pair
+        into ``forward_dec2_inputs``'s: t2 = relu(bn1.weight z1 + bn1.bias), res2 = bn_d.weight zd + bn_d.bias).  The trunk
+        runs exactly as in ``forward_dec2_inputs`` -- the same launches, power iteration (one per call), range-guard policy
+        and precision; only the epilogue vectors and the activation of the block's first launches differ."""
+        out = self._guarded_forward(x, False, features="dec2_normed")
+        for a in out:
+            if hasattr(a, "absmax"):
+                a.absmax = a.absmax.clone()
+        return out
+
     def _guarded_forward(self, x, return_intermediates, features=False):
         if x.dim() != 5 or x.shape[2] != self.in_channels:
             raise ValueError(f"expected x of shape [B,L,{self.in_channels},H,W], got {tuple(x.shape)}")
@@ -995,7 +1030,10 @@ class V2ce3d(nn.Module):
         of the last decoder block's conv2 and return its two inputs (forward_tail_inputs); features="normed": the same two launches
         without the BatchNorms' affine parts and the relu (forward_tail_normed); features="sources": stop in front of the last decoder
         block and return the two tensors it reads (forward_tail_sources); features="dec2": stop in front of conv2 of the decoder before
-        it and return that launch's two inputs and the last block's skip tensor (forward_dec2_inputs); the default launches are today's."""
+        it and return that launch's two inputs and the last block's skip tensor (forward_dec2_inputs); features="dec2_normed": the same
+        launches without the BatchNorms' affine parts and the relu (forward_dec2_normed); features="dec2_sources": stop in front of
+        that decoder and return the two tensors it reads and the last block's skip tensor (forward_dec2_sources); the default
+        launches are today's."""
         if self._prep is None:
             self._prepare()
         P, U = self._prep, self.UNet
@@ -1034,6 +1072,14 @@ class V2ce3d(nn.Module):
                 nxt = list(reversed(skips))[i + 1]
                 h = self._block_inputs_unfused(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4]))) + (nxt,)
                 break
+            if features == "dec2_normed" and i == len(U.decoders) - 2:
+                nxt = list(reversed(skips))[i + 1]
+                h = self._block_inputs_unfused(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])),
+                                               normed=True) + (nxt,)
+                break
+            if features == "dec2_sources" and i == len(U.decoders) - 2:
+                h = (h, skip, list(reversed(skips))[i + 1])
+                break
             if last and features == "sources":
                 h = (h, skip)
                 break
@@ -1044,7 +1090,7 @@ class V2ce3d(nn.Module):
             h = self._block(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])),
                             pred=fuse if last else None)
             inter[f"dec{i}"] = self.to_planar(h) if return_intermediates else None
-        if features in ("tail", "normed", "sources", "dec2"):
+        if features in ("tail", "normed", "sources", "dec2", "dec2_normed", "dec2_sources"):
             out = tuple(a if getattr(a, "c16", False) else self.to_c16(a) for a in h)
         elif features:
             # (the exact-f32 kernels produce planar tensors: one copy into the layout the head kernels take)
