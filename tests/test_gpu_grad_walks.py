@@ -24,8 +24,8 @@ output positions, one f32 ulp for the f64-throughout outputs), the worst element
 What this pins down: share arithmetic, halo reuse between tiles, the flush and the `stored` flag, the finish kernels' loops
 over 256 / 255 / 512 partial slots, the workspace at its largest.  Check B proves the rounding contract at scale; only
 check A detects a lost tile (on normal data at the deep row one tile moves an element by a fraction of its bound).
-Neither pins the chain length itself down: on integers any chain length is exact, and on normals a longer chain stays far
-inside the bound."""
+The chain length, the f64 sums above it, the f32 products and the per-element arithmetic are pinned down by the adversarial
+data of tests/test_gpu_grad_probes.py."""
 import functools
 
 import numpy as np
