@@ -4,7 +4,7 @@
  * The conventions of v2ce_hip.h hold: device pointers unless stated, entries enqueue on `stream` and do not synchronise,
  * they return V2CE_OK or a negative error code, v2ce_last_error() describes the last failure.
  *
- * v2ce_conv32_wgrad (csrc/convgrad.hip): the gradient of a stride-1, zero-padded 3x3x3 convolution 32 -> 32 with respect
+ * v2ce_conv32_wgrad (csrc/convnwgrad.hip): the gradient of a stride-1, zero-padded 3x3x3 convolution 32 -> 32 with respect
  * to its weight and to a per-channel shift added behind it, seen through the relu that follows.
  *   x, y, upstream  V2CE_LAYOUT_C16 with two channel groups: [B][L][2][H][pitch][16] f32, 16-byte aligned, B * L * 2 * H *
  *                   pitch * 64 bytes each; pitch >= W; the columns W .. pitch-1 of a row are never read.  x is the

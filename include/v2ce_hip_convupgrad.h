@@ -7,7 +7,7 @@
  * they return V2CE_OK or a negative error code, v2ce_last_error() describes the last failure.  The 32-channel entries of
  * v2ce_hip_convgrad.h and v2ce_hip_convdgrad.h are the layers behind this one; this header mirrors their refusals.
  *
- * v2ce_convup_wgrad (csrc/convupgrad.hip):
+ * v2ce_convup_wgrad (csrc/convupnwgrad.hip):
  *   x0          V2CE_LAYOUT_C16 with four channel groups at the SOURCE resolution: [B][L][4][H0][pitch0][16] f32 with
  *               H0 = (H + 1) / 2, W0 = (W + 1) / 2, pitch0 >= W0: the 64 channels the forward upsamples
  *   x1, g1, gd  V2CE_LAYOUT_C16 with two channel groups: [B][L][2][H][pitch][16] f32, pitch >= W.  x1 is the skip tensor

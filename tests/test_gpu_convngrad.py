@@ -15,7 +15,8 @@ the padding columns of d_x and d_res are zeros; d_x and d_res have the same byte
 Check B, contract.  Standard normals; d_weight and d_x inside the header's bounds (the worst element printed as a fraction
 of its bound), d_shift within one f32 ulp, d_res a copy.
 
-(32, 32): the bytes of conv32_wgrad / conv32_dgrad on the inputs of tests/golden/.lastconv, at the default grid and at a cap.
+(32, 32): conv32_wgrad / conv32_dgrad and the N-channel entries on the inputs of tests/golden/.lastconv, at the default grid
+and at two caps: the bytes recorded from the 32-channel kernels (tests/golden/.gradfold, tests/make_grad_fold_digests.py).
 Then y = None, each output alone, and the refusals of the checked entries."""
 import functools
 
@@ -26,6 +27,7 @@ import torch
 from tests import convn_ref as R
 from tests import grad_walk_ref as G
 from tests import last_conv_ref as CR
+from tests import make_grad_fold_digests as F
 from v2ce_toolbox_amd import dec2_conv, hip, last_conv
 
 pytestmark = pytest.mark.gpu
@@ -177,25 +179,20 @@ def test_without_y_and_each_output_alone(cin, cout):
         assert alone[name].lw == shape[3] and alone[name].c16
 
 
-@pytest.mark.parametrize("name", ["b2_l3_5x7", "b1_l2_3x70", "b1_l3_20x70"])
+@pytest.mark.parametrize("name", F.CASES)
 def test_32_to_32_gives_the_bytes_of_the_32_channel_entries(name):
-    c = CR.load_case(name)
-    W = c["t"].shape[4]
-    x, y, up = (torch.from_numpy(CR.to_c16(c[k], CR.pitch_of(W))).to(DEV) for k in ("t", "y", "upstream"))
-    for a in (x, y, up):
-        a.lw, a.c16 = W, True
-    gen = torch.Generator().manual_seed(5)
-    w = (torch.randn((32, 32, 3, 3, 3), generator=gen) * 0.1).to(DEV)
-    for cap in (0, 3):
-        old = last_conv.conv32_wgrad(x, y, up, max_workgroups=cap)
-        new = dec2_conv.convn_wgrad(x, y, up, max_workgroups=cap)
-        old.update(last_conv.conv32_dgrad(w, y, up, max_workgroups=cap))
-        new.update(dec2_conv.convn_dgrad(w, y, up, max_workgroups=cap))
-        for k in ("weight", "shift", "x", "res"):
-            assert same_bytes(old[k], new[k]), (name, cap, k, mismatch(new[k], old[k]))
-    plain_old = last_conv.conv32_wgrad(x, None, up)
-    plain_new = dec2_conv.convn_wgrad(x, None, up)
-    assert same_bytes(plain_old["weight"], plain_new["weight"]) and same_bytes(plain_old["shift"], plain_new["shift"])
+    """conv32_wgrad / conv32_dgrad forward to the kernels of convn_wgrad / convn_dgrad: both must still give the bytes that
+    the 32-channel kernels gave while they were kernels of their own (tests/make_grad_fold_digests.py), for every case, cap
+    and output, and so the bytes of each other."""
+    want = F.load()
+    old = F.conv32_outputs(name, last_conv.conv32_wgrad, last_conv.conv32_dgrad)
+    new = F.conv32_outputs(name, dec2_conv.convn_wgrad, dec2_conv.convn_dgrad)
+    keys = [k for k in want if k.startswith(f"conv32/{name}/")]
+    assert sorted(old) == sorted(new) == sorted(keys) and len(keys) == 4 * len(F.CONV32_CAPS) + 2
+    for k in keys:
+        assert same_bytes(old[k], new[k]), (k, mismatch(new[k], old[k]))
+        assert F.digest(old[k]) == want[k], (k, "conv32 entry: not the bytes of the 32-channel kernel")
+        assert F.digest(new[k]) == want[k], (k, "convn entry: not the bytes of the 32-channel kernel")
 
 
 def test_the_checked_entries_refuse_what_the_header_refuses():

@@ -15,8 +15,9 @@ bit for bit; the same bytes come out run to run, and each output requested alone
 Check B, contract.  Standard normals; d_weight and d_short inside the header's bound (the worst element printed as a
 fraction of its bound), d_short_bias within one f32 ulp.
 
-(64, 32, 32): the bytes of last_block.convup_wgrad on the inputs of tests/golden/.lastblock, at the default grid and at a
-cap.  Then the refusals of the checked entry."""
+(64, 32, 32): last_block.convup_wgrad and the N-channel entry on the inputs of tests/golden/.lastblock, at the default grid
+and at two caps: the bytes recorded from the 96 -> 32 kernel (tests/golden/.gradfold, tests/make_grad_fold_digests.py).
+Then the refusals of the checked entry."""
 import functools
 
 import numpy as np
@@ -25,7 +26,7 @@ import torch
 
 from tests import convupn_ref as R
 from tests import grad_walk_ref as G
-from tests import last_block_ref as LR
+from tests import make_grad_fold_digests as F
 from v2ce_toolbox_amd import dec2_block, hip, last_block
 
 pytestmark = pytest.mark.gpu
@@ -130,31 +131,20 @@ def test_normals_are_inside_the_header_bound(triple, run_):
            R.ulp32(t["d_short_bias"]))
 
 
-def lastblock_inputs(name):
-    z = LR.load_case(name)
-    W = z["x1"].shape[-1]
-    x0 = torch.from_numpy(LR.src_to_c16(z["x0"], LR.pitch_of((W + 1) // 2))).to(DEV)
-    x0.lw, x0.c16 = (W + 1) // 2, True
-    rest = []
-    for k in ("x1", "g1", "gd"):
-        a = torch.from_numpy(LR.to_c16(z[k], LR.pitch_of(W))).to(DEV)
-        a.lw, a.c16 = W, True
-        rest.append(a)
-    return (x0, *rest)
-
-
-@pytest.mark.parametrize("name", ["b2_l3_5x7", "b1_l2_3x70", "b1_l3_20x70"])
+@pytest.mark.parametrize("name", F.CASES)
 def test_64_32_32_gives_the_bytes_of_the_older_entry(name):
-    x0, x1, g1, gd = lastblock_inputs(name)
-    for cap in (0, 3, 7):
-        old = last_block.convup_wgrad(x0, x1, g1, gd, max_workgroups=cap)
-        new = dec2_block.convupn_wgrad(x0, x1, g1, gd, max_workgroups=cap)
-        torch.cuda.synchronize()
-        for k in KEYS:
-            assert same_bytes(old[k], new[k]), (name, cap, k, mismatch(new[k], old[k]))
-    short_old = last_block.convup_wgrad(x0, x1, None, gd, want=("short", "short_bias"))
-    short_new = dec2_block.convupn_wgrad(x0, x1, None, gd, want=("short", "short_bias"))
-    assert all(same_bytes(short_old[k], short_new[k]) for k in ("short", "short_bias"))
+    """convup_wgrad forwards to the kernel of convupn_wgrad: both must still give the bytes that the 96 -> 32 kernel gave
+    while it was a kernel of its own (tests/make_grad_fold_digests.py), for every case, cap and output, and so the bytes of
+    each other."""
+    want = F.load()
+    old = F.convup_outputs(name, last_block.convup_wgrad)
+    new = F.convup_outputs(name, dec2_block.convupn_wgrad)
+    keys = [k for k in want if k.startswith(f"convup/{name}/")]
+    assert sorted(old) == sorted(new) == sorted(keys) and len(keys) == len(KEYS) * len(F.CONVUP_CAPS) + 2
+    for k in keys:
+        assert same_bytes(old[k], new[k]), (k, mismatch(new[k], old[k]))
+        assert F.digest(old[k]) == want[k], (k, "convup entry: not the bytes of the 96 -> 32 kernel")
+        assert F.digest(new[k]) == want[k], (k, "convupn entry: not the bytes of the 96 -> 32 kernel")
 
 
 def test_a_nearest_upsample_that_is_not_the_half_map_is_refused(monkeypatch):

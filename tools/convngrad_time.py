@@ -1,6 +1,6 @@
 """Time the 64-channel gradient kernels of UNet.decoders[2].conv2 (v2ce_convn_wgrad, v2ce_convn_dgrad) at that layer's
-shape [1, 16, 130, 173] against the 32-channel kernels behind them (v2ce_conv32_wgrad, v2ce_conv32_dgrad) at the same
-positions, against torch's own route (conv3d weight / input gradients on planar f32, MIOpen, plus the layout copies a
+shape [1, 16, 130, 173] against the same kernels at 32 -> 32 through the 32-channel entries (v2ce_conv32_wgrad,
+v2ce_conv32_dgrad) at the same positions, against torch's own route (conv3d weight / input gradients on planar f32, MIOpen, plus the layout copies a
 channels-last-16 caller pays), and one fit_dec2_conv step next to one fit_last_block step at the default frame size.
 Prints one JSON line.
 

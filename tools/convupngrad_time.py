@@ -1,6 +1,6 @@
 """Time the weight-gradient kernel of UNet.decoders[2].conv1 and its shortcut (v2ce_convupn_wgrad at 128 + 64 -> 64, all three
-outputs) at that layer's shape [1, 16, 130, 173] against the kernel it restates (v2ce_convup_wgrad, 64 + 32 -> 32) at the last
-block's shape [1, 16, 260, 346] -- the two calls execute the same number of MFMA flops, 4 times the channel products over a
+outputs) at that layer's shape [1, 16, 130, 173] against the same kernel through the 64 + 32 -> 32 entry (v2ce_convup_wgrad) at
+the last block's shape [1, 16, 260, 346] -- the two calls execute the same number of MFMA flops, 4 times the channel products over a
 quarter of the positions, on almost the same tile count per workgroup --, against torch's own route (conv3d weight gradients
 on the materialised upsample + concat in planar f32, MIOpen, plus the layout copies a channels-last-16 caller pays), and one
 fit_dec2_block step next to one fit_dec2_conv step at the default frame size.  Prints one JSON line.

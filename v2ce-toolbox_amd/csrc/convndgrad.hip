@@ -1,18 +1,21 @@
 // convndgrad.hip -- the input gradient of a 3x3x3 Conv3d(cin, cout) with 32 or 64 channels on either side on gfx950, seen
-// through the relu behind it (include/v2ce_hip_convngrad.h states the formulas, the tensors and the precision contract).
-// UNet.decoders[2].conv2 is the 64 -> 64 case.
+// through the relu behind it (include/v2ce_hip_convngrad.h and, for the 32 -> 32 entry v2ce_conv32_dgrad,
+// include/v2ce_hip_convdgrad.h state the formulas, the tensors and the precision contract).  UNet.decoders[3].conv2 is the
+// 32 -> 32 case, UNet.decoders[2].conv2 the 64 -> 64 case.
 //
 // d_x is a GEMM with the positions as M, the input channels as N and (co group, tap, co) as K = 27 cout: per tap (kt, kh,
 // kw) a block D[pos][ci] += sum_co m[co][pos - tap + 1] W[co][ci][tap].  v_mfma_f32_32x32x2_f32 takes two output channels
-// per instruction: lane l holds A[pos = l & 31][k = l >> 5] and B[k = l >> 5][ci = l & 31].  The tile, the halo and the
-// bank arguments are convdgrad.hip's, because a workgroup still stages 32 channels at a time:
+// per instruction: lane l holds A[pos = l & 31][k = l >> 5] and B[k = l >> 5][ci = l & 31].  A workgroup stages 32 channels
+// at a time, whatever cin and cout are, so the tile, the halo and the bank arguments do not depend on them:
 //   B  the weights, [tap][co][ci] after the prep kernel.  A wave keeps those of its taps (wave v takes the taps 7 v .. 7 v
 //      + 6, the last wave six) for its 32 input channels and EVERY co group in registers for the whole kernel: 7 taps x 16
 //      k-steps = 112 registers per lane and co group, 224 at cout = 64.  With the 64 accumulator registers that is under
 //      the 512 a wave may hold at four waves per workgroup (one workgroup per CU: the LDS decides the occupancy anyway),
 //      and nothing is fetched again inside the tile walk
 //   A  the halo of m of ONE co group in LDS, channel-major: sH[co][halo position], 3 frames x 4 rows x 66 columns = 792
-//      positions at a plane stride of kPlane = 800 floats (= 32 mod 64): one conflict-free ds_read_b32 per MFMA
+//      positions at a plane stride of kPlane = 800 floats (= 32 mod 64).  The 32 lanes of a half read 32 consecutive
+//      columns of one row of one channel plane (consecutive banks); the other half reads the next plane, 32 banks further:
+//      one conflict-free ds_read_b32 per MFMA
 //
 // The grid is (cin / 32) x shares: workgroup s * gi + cig walks share s of the tiles for the input channels 32 cig .. + 31,
 // so one workgroup produces a whole d_x element.  A tile is 2 rows x 64 columns of one frame: four M groups of 32
@@ -26,52 +29,29 @@
 //   3. writes the four partial tiles over the halo (sP[wave][position][ci], 64 KB) and adds them in the order of the waves,
 //      ((p0 + p1) + p2) + p3, one thread per four channels of a position, into d_x.
 // An element's order of summation is fixed by cout and the tap split alone: it depends neither on the grid nor on the tile
-// walk.  With cin = cout = 32 every step is convdgrad.hip's.
-#include "common.h"
+// walk.  At 32 -> 32 there is one ci group and one co group: the grid is the shares, and a tile's halo is staged once.
+#include "convgrad_dev.h"
 
+#include "../../include/v2ce_hip_convdgrad.h"
 #include "../../include/v2ce_hip_convngrad.h"
 
 namespace v2ce {
 namespace {
 
-constexpr int kThreads = 256;                       // 4 waves
-constexpr int kC = 32;                              // channels of a group on either side
-constexpr int kTaps = 27;
 constexpr int kTapsPerWave = 7;
 constexpr int kSteps = kC / 2;                      // k-steps of a tap and co group: two output channels per MFMA
-constexpr int kTileH = 2, kTileW = 64, kTile = kTileH * kTileW;
 constexpr int kGroups = kTile / 32;                 // M groups of a tile: (row, half of the columns)
-constexpr int kHaloT = 3, kHaloH = kTileH + 2, kHaloW = kTileW + 2;
-constexpr int kHalo = kHaloT * kHaloH * kHaloW;     // 792 positions
-constexpr int kPlane = 800;                         // floats between the channel planes of sH
-constexpr int kMaxGrid = 256;                       // one workgroup per CU: 100 KB of LDS each
-constexpr size_t kLds = (size_t)kC * kPlane * sizeof(float);
-static_assert(kPlane >= kHalo && kPlane % 64 == 32, "plane stride: the two halves of a wave on disjoint banks");
+constexpr size_t kLds = (size_t)kC * kPlane * sizeof(float);            // 100 KB
 static_assert((size_t)4 * kTile * kC * sizeof(float) <= kLds, "the partial tiles lie over the halo");
 static_assert(kLds <= 160 * 1024, "LDS of one workgroup");
+static_assert(V2CE_DGRAD_TERMS == kTaps * kC, "terms of an element of d_x at 32 -> 32 (27 * 32)");
 static_assert(kTapsPerWave * 4 >= kTaps && kTapsPerWave * 3 < kTaps, "every wave has a tap");
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct Dims {
-    int B, L, H, W, pitch;
+struct Dims : Extent {
     int cin, cout, gi;                              // gi: groups of 32 input channels
-    int tiles_h, tiles_w;
-    long long tiles;                                // B L tiles_h tiles_w
     int shares;
     size_t total;
 };
-
-// float offset of plane g (16 channels) of (frame, row, column) in a C16 tensor with `planes` planes
-__device__ __forceinline__ long long c16_at(const Dims &D, int planes, long long f, int g, int h, int w) {
-    return ((((f * planes + g) * D.H + h) * D.pitch) + w) * 16;
-}
-
-__device__ __forceinline__ float4 relu_mask(float4 u, float4 yv) {
-    u.x = yv.x > 0.0f ? u.x : 0.0f; u.y = yv.y > 0.0f ? u.y : 0.0f;
-    u.z = yv.z > 0.0f ? u.z : 0.0f; u.w = yv.w > 0.0f ? u.w : 0.0f;
-    return u;
-}
 
 // [co][ci][27] -> [tap][co][ci]: what a lane of the main kernel loads as consecutive floats
 __global__ __launch_bounds__(kThreads) void ndgrad_prep_kernel(const float *__restrict__ weight, int cin, int cout,
@@ -118,11 +98,9 @@ __global__ __launch_bounds__(kThreads) void ndgrad_kernel(const float *__restric
     }
 
     for (long long tile = t0; tile < t1; ++tile) {
-        const int tw = (int)(tile % D.tiles_w);
-        const long long r1 = tile / D.tiles_w;
-        const int th = (int)(r1 % D.tiles_h);
-        const long long f = r1 / D.tiles_h;          // frame b L + l
-        const int l = (int)(f % D.L), h0 = th * kTileH, w0 = tw * kTileW;
+        const TileAt ta = tile_at(D, tile);
+        const long long f = ta.f;
+        const int l = ta.l, h0 = ta.h0, w0 = ta.w0, tw = ta.tw;
 
         f32x16 acc[kGroups];
 #pragma unroll
@@ -243,54 +221,31 @@ __global__ __launch_bounds__(kThreads) void ndgrad_kernel(const float *__restric
 
 bool make_dims(int cin, int cout, int B, int L, int H, int W, int pitch, int max_workgroups, Dims &D) {
     if ((cin != 32 && cin != 64) || (cout != 32 && cout != 64)) return false;
-    if (B < 1 || L < 1 || H < 1 || W < 1 || pitch < W || max_workgroups < 0) return false;
-    const long long N = (long long)B * L * H * W;
-    if ((long long)B * L >= (1ll << 31) || (long long)H * W >= (1ll << 31) || N >= (1ll << 31)) return false;
-    if ((long long)B * L * H >= (1ll << 34) || (long long)B * L * H * pitch >= (1ll << 34)) return false;
-    D.B = B; D.L = L; D.H = H; D.W = W; D.pitch = pitch;
+    if (!make_extent(B, L, H, W, pitch, false, 0, max_workgroups, D)) return false;
     D.cin = cin; D.cout = cout; D.gi = cin / kC;
-    D.tiles_h = (H + kTileH - 1) / kTileH;
-    D.tiles_w = (W + kTileW - 1) / kTileW;
-    D.tiles = (long long)B * L * D.tiles_h * D.tiles_w;
-    const long long most = kMaxGrid / D.gi;
-    long long shares = D.tiles < most ? D.tiles : most;
-    const long long cap = max_workgroups / D.gi > 1 ? max_workgroups / D.gi : 1;
-    if (max_workgroups > 0 && shares > cap) shares = cap;
-    D.shares = (int)shares;
-    D.total = ((size_t)kTaps * cout * cin * sizeof(float) + 255) & ~(size_t)255;   // the repacked weight; the grid needs nothing
+    D.shares = plan_shares(D.tiles, D.gi, max_workgroups);
+    D.total = round256((size_t)kTaps * cout * cin * sizeof(float));     // the repacked weight; the grid needs nothing
     return true;
 }
 
 const char *kNeeds = "needs cin, cout in {32, 64}, B, L, H, W >= 1, pitch >= W, max_workgroups >= 0, B L H W < 2^31 and "
                      "B L H pitch < 2^34";
 
-}  // namespace
-}  // namespace v2ce
-
-using namespace v2ce;
-
-extern "C" size_t v2ce_convn_dgrad_workspace_bytes(int cin, int cout, int B, int L, int H, int W, int pitch, int max_workgroups) {
-    Dims D;
-    return make_dims(cin, cout, B, L, H, W, pitch, max_workgroups, D) ? D.total : 0;
-}
-
-extern "C" int v2ce_convn_dgrad(const float *weight, const float *y, const float *upstream, int cin, int cout, int B, int L, int H,
-                                int W, int pitch, float *d_x, float *d_res, void *workspace, size_t workspace_bytes,
-                                int max_workgroups, v2ce_stream_t stream) {
+// `entry`: the symbol the caller used; it leads every message
+int ndgrad(const char *entry, const float *weight, const float *y, const float *upstream, int cin, int cout, int B, int L, int H,
+           int W, int pitch, float *d_x, float *d_res, void *workspace, size_t workspace_bytes, int max_workgroups,
+           v2ce_stream_t stream) {
     clear_error();
     Dims D;
     V2CE_REQUIRE(make_dims(cin, cout, B, L, H, W, pitch, max_workgroups, D), V2CE_ERR_BAD_ARG,
-                 "v2ce_convn_dgrad: cin %d cout %d B %d L %d H %d W %d pitch %d max_workgroups %d: %s", cin, cout, B, L, H, W, pitch,
+                 "%s: cin %d cout %d B %d L %d H %d W %d pitch %d max_workgroups %d: %s", entry, cin, cout, B, L, H, W, pitch,
                  max_workgroups, kNeeds);
-    V2CE_REQUIRE(weight && upstream && workspace, V2CE_ERR_BAD_ARG, "v2ce_convn_dgrad: null pointer");
-    V2CE_REQUIRE(d_x || d_res, V2CE_ERR_BAD_ARG, "v2ce_convn_dgrad: no output requested (d_x and d_res are both null)");
-    V2CE_REQUIRE(aligned16(y, upstream, d_x, d_res), V2CE_ERR_BAD_ARG,
-                 "v2ce_convn_dgrad: y, upstream, d_x and d_res must be 16-byte aligned");
-    V2CE_REQUIRE((reinterpret_cast<uintptr_t>(weight) & 3) == 0, V2CE_ERR_BAD_ARG, "v2ce_convn_dgrad: weight must be 4-byte aligned");
-    V2CE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, V2CE_ERR_BAD_ARG,
-                 "v2ce_convn_dgrad: workspace must be 8-byte aligned");
-    V2CE_REQUIRE(workspace_bytes >= D.total, V2CE_ERR_WORKSPACE, "v2ce_convn_dgrad: workspace too small (%zu < %zu)",
-                 workspace_bytes, D.total);
+    V2CE_REQUIRE(weight && upstream && workspace, V2CE_ERR_BAD_ARG, "%s: null pointer", entry);
+    V2CE_REQUIRE(d_x || d_res, V2CE_ERR_BAD_ARG, "%s: no output requested (d_x and d_res are both null)", entry);
+    V2CE_REQUIRE(aligned16(y, upstream, d_x, d_res), V2CE_ERR_BAD_ARG, "%s: y, upstream, d_x and d_res must be 16-byte aligned",
+                 entry);
+    V2CE_REQUIRE((reinterpret_cast<uintptr_t>(weight) & 3) == 0, V2CE_ERR_BAD_ARG, "%s: weight must be 4-byte aligned", entry);
+    if (const int rc = check_workspace(entry, workspace, workspace_bytes, D.total)) return rc;
     hipStream_t st = as_stream(stream);
     float *wt = static_cast<float *>(workspace);
     const auto kernel = cout == 64 ? ndgrad_kernel<2> : ndgrad_kernel<1>;
@@ -305,4 +260,33 @@ extern "C" int v2ce_convn_dgrad(const float *weight, const float *y, const float
                        d_res);
     V2CE_HIP_CHECK(hipGetLastError());
     return V2CE_OK;
+}
+
+}  // namespace
+}  // namespace v2ce
+
+using namespace v2ce;
+
+extern "C" size_t v2ce_convn_dgrad_workspace_bytes(int cin, int cout, int B, int L, int H, int W, int pitch, int max_workgroups) {
+    Dims D;
+    return make_dims(cin, cout, B, L, H, W, pitch, max_workgroups, D) ? D.total : 0;
+}
+
+extern "C" int v2ce_convn_dgrad(const float *weight, const float *y, const float *upstream, int cin, int cout, int B, int L, int H,
+                                int W, int pitch, float *d_x, float *d_res, void *workspace, size_t workspace_bytes,
+                                int max_workgroups, v2ce_stream_t stream) {
+    return ndgrad("v2ce_convn_dgrad", weight, y, upstream, cin, cout, B, L, H, W, pitch, d_x, d_res, workspace, workspace_bytes,
+                  max_workgroups, stream);
+}
+
+// the 32 -> 32 entries of include/v2ce_hip_convdgrad.h: ndgrad_kernel<1> with one ci group
+extern "C" size_t v2ce_conv32_dgrad_workspace_bytes(int B, int L, int H, int W, int pitch, int max_workgroups) {
+    return v2ce_convn_dgrad_workspace_bytes(32, 32, B, L, H, W, pitch, max_workgroups);
+}
+
+extern "C" int v2ce_conv32_dgrad(const float *weight, const float *y, const float *upstream, int B, int L, int H, int W, int pitch,
+                                 float *d_x, float *d_res, void *workspace, size_t workspace_bytes, int max_workgroups,
+                                 v2ce_stream_t stream) {
+    return ndgrad("v2ce_conv32_dgrad", weight, y, upstream, 32, 32, B, L, H, W, pitch, d_x, d_res, workspace, workspace_bytes,
+                  max_workgroups, stream);
 }

@@ -1,63 +1,50 @@
 // convnwgrad.hip -- the weight gradient of a 3x3x3 Conv3d(cin, cout) with 32 or 64 channels on either side on gfx950, seen
-// through the relu behind it (include/v2ce_hip_convngrad.h states the formulas, the tensors and the precision contract).
-// UNet.decoders[2].conv2 is the 64 -> 64 case.
+// through the relu behind it (include/v2ce_hip_convngrad.h and, for the 32 -> 32 entry v2ce_conv32_wgrad,
+// include/v2ce_hip_convgrad.h state the formulas, the tensors and the precision contract).  UNet.decoders[3].conv2 is the
+// 32 -> 32 case, UNet.decoders[2].conv2 the 64 -> 64 case.
 //
-// The tile is convgrad.hip's, run once per pair of channel groups: d_weight is (cout / 32) x (cin / 32) blocks of the
-// 32 x 864 GEMM of the 32-channel kernel.  Per tap (kt, kh, kw) a 32 x 32 block D[co][ci] += sum_pos m[co][pos] x[ci][pos +
-// tap] on v_mfma_f32_32x32x2_f32, two positions per instruction: lane l holds A[co = l & 31][k = l >> 5] and B[k = l >> 5]
-// [ci = l & 31], both staged in LDS as [position][32 channels], one conflict-free ds_read_b32 each.
+// d_weight is (cout / 32) x (cin / 32) blocks of a 32 x 864 GEMM whose K runs over every output position, one block per pair
+// of channel groups.  Per tap (kt, kh, kw) a 32 x 32 block D[co][ci] += sum_pos m[co][pos] x[ci][pos + tap].
+// v_mfma_f32_32x32x2_f32 takes two positions per instruction: lane l holds A[co = l & 31][k = l >> 5] and B[k = l >> 5]
+// [ci = l & 31], so with both operands staged in LDS as [position][32 channels] a wave's A operand of the position pair
+// (p, p + 1) is the 64 consecutive floats at p * 32 and its B operand the 64 consecutive floats at (halo position of p
+// shifted by the tap) * 32: one conflict-free ds_read_b32 each.
 //
 // The grid is pairs x shares: workgroup s * pairs + p walks share s of the tiles for pair p = cog * (cin / 32) + cig, the
-// output channels 32 cog .. + 31 against the input channels 32 cig .. + 31.  A tile is 2 rows x 64 columns of one frame
-// (kTile = 128 positions).  Per tile the workgroup stages
+// output channels 32 cog .. + 31 against the input channels 32 cig .. + 31; 32 -> 32 has one pair, and its grid is the
+// shares.  A tile is 2 rows x 64 columns of one frame (kTile = 128 positions, convgrad_dev.h).  Per tile the workgroup stages
 //   sM  m = y > 0 ? upstream : 0 of its 32 output channels, [128][32] f32 (16 KB); zeros outside the tensor
 //   sX  the halo of its 32 input channels of x, 3 frames x 4 rows x 66 columns, [792][32] f32 (99 KB); zeros outside the
 //       frame, the sequence or the row's W columns -- the convolution's zero padding
-// and wave v takes the taps 7 v .. 7 v + 6 (the last wave six), 7 x 16 accumulator registers per lane.  A workgroup stages
-// 32 channels of either tensor at a time, so the LDS budget and the bank arguments are those of the 32-channel kernel.
+// and wave v takes the taps 7 v .. 7 v + 6 (the last wave six): per position pair one read of sM and one read of sX per tap
+// feed one MFMA per tap, 7 x 16 accumulator registers per lane.  LDS traffic is 8 reads per 7 MFMAs of 64 cycles.  A
+// workgroup stages 32 channels of either tensor at a time, whatever cin and cout are.
 //
 // Chain and flush: an f32 accumulator takes kChainTiles = V2CE_WGRAD_CHAIN / 128 tiles; then (and after the last tile) the
 // lane that owns it adds it into the workgroup's f64 partial in the workspace (the first flush stores) and clears it.  A
 // partial element has one owner for the whole kernel, so no atomics.  d_shift is taken by the pairs with cig = 0: thread t
 // sums channel t & 31 over the 16 positions (t >> 5) * 16 .. + 15 of sM in f64, tile after tile; the eight sums of a
 // channel meet at the end in a fixed order.  finish_kernel: one thread per output adds its pair's partials in the order of
-// the shares 0 .. shares - 1 and rounds once.  With one pair (cin = cout = 32) every step is convgrad.hip's.
-#include "common.h"
+// the shares 0 .. shares - 1 and rounds once.
+#include "convgrad_dev.h"
 
 #include "../../include/v2ce_hip_convngrad.h"
 
 namespace v2ce {
 namespace {
 
-constexpr int kThreads = 256;                       // 4 waves
-constexpr int kC = 32;                              // channels of a group on either side
-constexpr int kTaps = 27;
 constexpr int kTapsPerWave = 7;
-constexpr int kTileH = 2, kTileW = 64, kTile = kTileH * kTileW;
-constexpr int kHaloT = 3, kHaloH = kTileH + 2, kHaloW = kTileW + 2;
-constexpr int kHalo = kHaloT * kHaloH * kHaloW;     // 792 positions
 constexpr int kChainTiles = V2CE_WGRAD_CHAIN / kTile;
-constexpr int kMaxGrid = 256;                       // one workgroup per CU: 115 KB of LDS each
 constexpr int kPartial = kTaps * kC * kC + kC;      // f64 per workgroup: [27][32][32] d_weight blocks, [32] d_shift
-constexpr size_t kLds = (size_t)(kTile + kHalo) * kC * sizeof(float);
+constexpr size_t kLds = (size_t)(kTile + kHalo) * kC * sizeof(float);   // 115 KB
 static_assert(kChainTiles >= 1 && kChainTiles * kTile <= V2CE_WGRAD_CHAIN && V2CE_WGRAD_CHAIN <= 4096, "chain length");
 static_assert(kLds <= 160 * 1024, "LDS of one workgroup");
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct Dims {
-    int B, L, H, W, pitch;
+struct Dims : Extent {
     int cin, cout, gi, go, pairs;                   // gi, go: groups of 32 input / output channels; pairs = gi go
-    int tiles_h, tiles_w;
-    long long tiles;                                // B L tiles_h tiles_w
     int shares;
     size_t total;
 };
-
-// float offset of plane g (16 channels) of (frame, row, column) in a C16 tensor with `planes` planes
-__device__ __forceinline__ long long c16_at(const Dims &D, int planes, long long f, int g, int h, int w) {
-    return ((((f * planes + g) * D.H + h) * D.pitch) + w) * 16;
-}
 
 __global__ __launch_bounds__(kThreads) void nwgrad_kernel(const float *__restrict__ x, const float *__restrict__ y,
                                                           const float *__restrict__ up, Dims D, int doW, int wantB,
@@ -91,30 +78,12 @@ __global__ __launch_bounds__(kThreads) void nwgrad_kernel(const float *__restric
     bool stored = false;
 
     for (long long tile = t0; tile < t1; ++tile) {
-        const int tw = (int)(tile % D.tiles_w);
-        const long long r1 = tile / D.tiles_w;
-        const int th = (int)(r1 % D.tiles_h);
-        const long long f = r1 / D.tiles_h;          // frame b L + l
-        const int l = (int)(f % D.L), h0 = th * kTileH, w0 = tw * kTileW;
+        const TileAt ta = tile_at(D, tile);
+        const long long f = ta.f;
+        const int l = ta.l, h0 = ta.h0, w0 = ta.w0;
 
         __syncthreads();                             // the previous tile has been read
-        // m: 128 positions x 8 pieces of 16 bytes
-#pragma unroll
-        for (int k = 0; k < kTile * 8 / kThreads; ++k) {
-            const int i = t + k * kThreads, piece = i & 3, rest = i >> 2, g = rest / kTile, p = rest % kTile;
-            const int h = h0 + p / kTileW, w = w0 + p % kTileW;
-            float4 mv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (h < D.H && w < D.W) {
-                const long long at = c16_at(D, mplanes, f, cog * 2 + g, h, w) + piece * 4;
-                mv = *reinterpret_cast<const float4 *>(up + at);
-                if (y) {
-                    const float4 yv = *reinterpret_cast<const float4 *>(y + at);
-                    mv.x = yv.x > 0.0f ? mv.x : 0.0f; mv.y = yv.y > 0.0f ? mv.y : 0.0f;
-                    mv.z = yv.z > 0.0f ? mv.z : 0.0f; mv.w = yv.w > 0.0f ? mv.w : 0.0f;
-                }
-            }
-            *reinterpret_cast<float4 *>(sM + p * kC + g * 16 + piece * 4) = mv;
-        }
+        stage_tile(D, up, y, sM, mplanes, cog * 2, f, h0, w0, t);
         if (doW) {
             // the halo of x: 792 positions x 8 pieces
 #pragma unroll 5
@@ -148,11 +117,7 @@ __global__ __launch_bounds__(kThreads) void nwgrad_kernel(const float *__restric
                 }
             }
         }
-        if (doB) {
-            const float *row = sM + (t >> 5) * 16 * kC + (t & 31);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) bsum += (double)row[i * kC];
-        }
+        if (doB) add_channel_part(sM, t, bsum);
 
         if (doW && (++chain == kChainTiles || tile + 1 == t1)) {
             // C/D map of the 32x32 MFMA: column (ci) = lane & 31, row (co) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
@@ -174,19 +139,7 @@ __global__ __launch_bounds__(kThreads) void nwgrad_kernel(const float *__restric
         }
     }
 
-    if (doB) {
-        // channel t & 31: parts 2 wv (lanes 0 .. 31) and 2 wv + 1 (lanes 32 .. 63); summed in the order of the parts
-        double *red = reinterpret_cast<double *>(smem);
-        __syncthreads();
-        red[t] = bsum;
-        __syncthreads();
-        if (t < kC) {
-            double s = red[t];
-#pragma unroll
-            for (int part = 1; part < kThreads / kC; ++part) s += red[part * kC + t];
-            mine[kTaps * kC * kC + t] = s;
-        }
-    }
+    if (doB) reduce_channel_parts(reinterpret_cast<double *>(smem), t, bsum, mine + kTaps * kC * kC);
 }
 
 // one thread per output: e < pairs * 27 * 1024 is d_weight (e = (pair * 27 + tap) * 1024 + co * 32 + ci inside the pair's
@@ -212,26 +165,42 @@ __global__ __launch_bounds__(kThreads) void nwgrad_finish_kernel(const double *_
 
 bool make_dims(int cin, int cout, int B, int L, int H, int W, int pitch, int max_workgroups, Dims &D) {
     if ((cin != 32 && cin != 64) || (cout != 32 && cout != 64)) return false;
-    if (B < 1 || L < 1 || H < 1 || W < 1 || pitch < W || max_workgroups < 0) return false;
-    const long long N = (long long)B * L * H * W;
-    if ((long long)B * L >= (1ll << 31) || (long long)H * W >= (1ll << 31) || N >= (1ll << 31)) return false;
-    if ((long long)B * L * H >= (1ll << 34) || (long long)B * L * H * pitch >= (1ll << 34)) return false;
-    D.B = B; D.L = L; D.H = H; D.W = W; D.pitch = pitch;
+    if (!make_extent(B, L, H, W, pitch, false, 0, max_workgroups, D)) return false;
     D.cin = cin; D.cout = cout; D.gi = cin / kC; D.go = cout / kC; D.pairs = D.gi * D.go;
-    D.tiles_h = (H + kTileH - 1) / kTileH;
-    D.tiles_w = (W + kTileW - 1) / kTileW;
-    D.tiles = (long long)B * L * D.tiles_h * D.tiles_w;
-    const long long most = kMaxGrid / D.pairs;
-    long long shares = D.tiles < most ? D.tiles : most;
-    const long long cap = max_workgroups / D.pairs > 1 ? max_workgroups / D.pairs : 1;
-    if (max_workgroups > 0 && shares > cap) shares = cap;
-    D.shares = (int)shares;
-    D.total = (((size_t)D.shares * D.pairs * kPartial * sizeof(double)) + 255) & ~(size_t)255;
+    D.shares = plan_shares(D.tiles, D.pairs, max_workgroups);
+    D.total = round256((size_t)D.shares * D.pairs * kPartial * sizeof(double));
     return true;
 }
 
 const char *kNeeds = "needs cin, cout in {32, 64}, B, L, H, W >= 1, pitch >= W, max_workgroups >= 0, B L H W < 2^31 and "
                      "B L H pitch < 2^34";
+
+// `entry`: the symbol the caller used; it leads every message
+int nwgrad(const char *entry, const float *x, const float *y, const float *upstream, int cin, int cout, int B, int L, int H, int W,
+           int pitch, float *d_weight, float *d_shift, void *workspace, size_t workspace_bytes, int max_workgroups,
+           v2ce_stream_t stream) {
+    clear_error();
+    Dims D;
+    V2CE_REQUIRE(make_dims(cin, cout, B, L, H, W, pitch, max_workgroups, D), V2CE_ERR_BAD_ARG,
+                 "%s: cin %d cout %d B %d L %d H %d W %d pitch %d max_workgroups %d: %s", entry, cin, cout, B, L, H, W, pitch,
+                 max_workgroups, kNeeds);
+    V2CE_REQUIRE(x && upstream && workspace, V2CE_ERR_BAD_ARG, "%s: null pointer", entry);
+    V2CE_REQUIRE(d_weight || d_shift, V2CE_ERR_BAD_ARG, "%s: no output requested (d_weight and d_shift are both null)", entry);
+    V2CE_REQUIRE(aligned16(x, y, upstream), V2CE_ERR_BAD_ARG, "%s: x, y and upstream must be 16-byte aligned", entry);
+    if (const int rc = check_workspace(entry, workspace, workspace_bytes, D.total)) return rc;
+    hipStream_t st = as_stream(stream);
+    double *partial = static_cast<double *>(workspace);
+    const int doW = d_weight != nullptr, doB = d_shift != nullptr;
+    const int outputs = D.pairs * kTaps * kC * kC + D.cout;
+    V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(nwgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)kLds));
+    hipLaunchKernelGGL(nwgrad_kernel, dim3((unsigned)(D.shares * D.pairs)), dim3(kThreads), kLds, st, x, y, upstream, D, doW, doB,
+                       partial);
+    hipLaunchKernelGGL(nwgrad_finish_kernel, dim3((outputs + kThreads - 1) / kThreads), dim3(kThreads), 0, st, partial, D, doW,
+                       doB, d_weight, d_shift);
+    V2CE_HIP_CHECK(hipGetLastError());
+    return V2CE_OK;
+}
 
 }  // namespace
 }  // namespace v2ce
@@ -246,29 +215,18 @@ extern "C" size_t v2ce_convn_wgrad_workspace_bytes(int cin, int cout, int B, int
 extern "C" int v2ce_convn_wgrad(const float *x, const float *y, const float *upstream, int cin, int cout, int B, int L, int H,
                                 int W, int pitch, float *d_weight, float *d_shift, void *workspace, size_t workspace_bytes,
                                 int max_workgroups, v2ce_stream_t stream) {
-    clear_error();
-    Dims D;
-    V2CE_REQUIRE(make_dims(cin, cout, B, L, H, W, pitch, max_workgroups, D), V2CE_ERR_BAD_ARG,
-                 "v2ce_convn_wgrad: cin %d cout %d B %d L %d H %d W %d pitch %d max_workgroups %d: %s", cin, cout, B, L, H, W, pitch,
-                 max_workgroups, kNeeds);
-    V2CE_REQUIRE(x && upstream && workspace, V2CE_ERR_BAD_ARG, "v2ce_convn_wgrad: null pointer");
-    V2CE_REQUIRE(d_weight || d_shift, V2CE_ERR_BAD_ARG,
-                 "v2ce_convn_wgrad: no output requested (d_weight and d_shift are both null)");
-    V2CE_REQUIRE(aligned16(x, y, upstream), V2CE_ERR_BAD_ARG, "v2ce_convn_wgrad: x, y and upstream must be 16-byte aligned");
-    V2CE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, V2CE_ERR_BAD_ARG,
-                 "v2ce_convn_wgrad: workspace must be 8-byte aligned");
-    V2CE_REQUIRE(workspace_bytes >= D.total, V2CE_ERR_WORKSPACE, "v2ce_convn_wgrad: workspace too small (%zu < %zu)",
-                 workspace_bytes, D.total);
-    hipStream_t st = as_stream(stream);
-    double *partial = static_cast<double *>(workspace);
-    const int doW = d_weight != nullptr, doB = d_shift != nullptr;
-    const int outputs = D.pairs * kTaps * kC * kC + D.cout;
-    V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(nwgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)kLds));
-    hipLaunchKernelGGL(nwgrad_kernel, dim3((unsigned)(D.shares * D.pairs)), dim3(kThreads), kLds, st, x, y, upstream, D, doW, doB,
-                       partial);
-    hipLaunchKernelGGL(nwgrad_finish_kernel, dim3((outputs + kThreads - 1) / kThreads), dim3(kThreads), 0, st, partial, D, doW,
-                       doB, d_weight, d_shift);
-    V2CE_HIP_CHECK(hipGetLastError());
-    return V2CE_OK;
+    return nwgrad("v2ce_convn_wgrad", x, y, upstream, cin, cout, B, L, H, W, pitch, d_weight, d_shift, workspace, workspace_bytes,
+                  max_workgroups, stream);
+}
+
+// the 32 -> 32 entries of include/v2ce_hip_convgrad.h: one pair
+extern "C" size_t v2ce_conv32_wgrad_workspace_bytes(int B, int L, int H, int W, int pitch, int max_workgroups) {
+    return v2ce_convn_wgrad_workspace_bytes(32, 32, B, L, H, W, pitch, max_workgroups);
+}
+
+extern "C" int v2ce_conv32_wgrad(const float *x, const float *y, const float *upstream, int B, int L, int H, int W, int pitch,
+                                 float *d_weight, float *d_shift, void *workspace, size_t workspace_bytes, int max_workgroups,
+                                 v2ce_stream_t stream) {
+    return nwgrad("v2ce_conv32_wgrad", x, y, upstream, 32, 32, B, L, H, W, pitch, d_weight, d_shift, workspace, workspace_bytes,
+                  max_workgroups, stream);
 }

@@ -3,7 +3,7 @@
 // upsample that the forward never materialises (include/v2ce_hip_convupdgrad.h states the formulas, the tensors and the
 // precision contract).
 //
-// This is convdgrad.hip's kernel, once per 32-channel group of X = cat(upsample(x0), x1).  d_X of a group is a GEMM with the
+// The tile is convndgrad.hip's, once per 32-channel group of X = cat(upsample(x0), x1).  d_X of a group is a GEMM with the
 // positions as M, the group's 32 input channels as N and (unit, co) as K = 28 x 32: unit u < 27 is tap u of conv1 on g1,
 //   D[pos][ci] += sum_co g1[co][pos - tap + 1] W[co][ci][tap],
 // and unit 27 the shortcut on gd at the position itself.  v_mfma_f32_32x32x2_f32 takes two output channels per instruction:
@@ -28,32 +28,23 @@
 //      positions although their convolution sums are not zero -- and store 32 source columns of one source row.
 // An element's order of summation is fixed by the unit split and the pool order alone: it depends neither on the grid nor on
 // the tile walk nor on which other output was asked for.
-#include "common.h"
+#include "convgrad_dev.h"
 
 #include "../../include/v2ce_hip_convupdgrad.h"
 
 namespace v2ce {
 namespace {
 
-constexpr int kThreads = 256;                       // 4 waves
-constexpr int kC = 32;
 constexpr int kCin = 96;
 constexpr int kXGroups = 3;                         // 32-channel groups of X
-constexpr int kTaps = 27;
 constexpr int kUnits = kTaps + 1;                   // the 27 taps of conv1 and the shortcut
 constexpr int kUnitsPerWave = 7;
 constexpr int kSteps = kC / 2;                      // k-steps of a unit: two output channels per MFMA
-constexpr int kTileH = 2, kTileW = 64, kTile = kTileH * kTileW;
 constexpr int kMGroups = kTile / 32;                // M groups of a tile: (row, half of the columns)
-constexpr int kHaloT = 3, kHaloH = kTileH + 2, kHaloW = kTileW + 2;
-constexpr int kHalo = kHaloT * kHaloH * kHaloW;     // 792 positions
-constexpr int kPlane = 800;                         // floats between the channel planes of sH
 constexpr int kPlaneD = 160;                        // floats between the channel planes of sD
 constexpr int kPos = 36;                            // floats between the positions of a partial tile (32 channels + 4: 16-byte rows)
-constexpr int kMaxGrid = 256;                       // one workgroup per CU: 120 KB of LDS each
 constexpr int kWeights = kXGroups * kUnits * kC * kC;
-constexpr size_t kLds = (size_t)kC * (kPlane + kPlaneD) * sizeof(float);
-static_assert(kPlane >= kHalo && kPlane % 64 == 32, "plane stride: the two halves of a wave on disjoint banks");
+constexpr size_t kLds = (size_t)kC * (kPlane + kPlaneD) * sizeof(float);        // 120 KB
 static_assert(kPlaneD >= kTile && kPlaneD % 64 == 32, "plane stride of the gd tile");
 static_assert((size_t)4 * kTile * kPos <= (size_t)kC * kPlane && kPos % 4 == 0, "the partial tiles lie over the halo");
 static_assert(kLds <= 160 * 1024, "LDS of one workgroup");
@@ -61,21 +52,11 @@ static_assert(V2CE_UPDGRAD_TERMS == kUnits * kC, "terms of an element of d_X");
 static_assert(kUnits == 4 * kUnitsPerWave, "every wave owns seven units");
 static_assert(kTileH == 2 && kTileW % 2 == 0 && kTileW / 2 * kC / 4 == kThreads, "one thread per four channels of a source pixel");
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct Dims {
-    int B, L, H, W, pitch, H0, W0, pitch0;
-    int tiles_h, tiles_w;
-    long long tiles;                                // B L tiles_h tiles_w
+struct Dims : Extent {
     size_t total;
 };
 
-// float offset of channel group g of (frame, row, column) in the two-group C16 tensors g1, gd, d_x1
-__device__ __forceinline__ long long c16_at(const Dims &D, long long f, int g, int h, int w) {
-    return ((((f * 2 + g) * D.H + h) * D.pitch) + w) * 16;
-}
-
-// the same in the four-group d_x0, (h0, w0) at the source resolution
+// c16_at (g1, gd and d_x1 have two planes) in the four-plane d_x0, (h0, w0) at the source resolution
 __device__ __forceinline__ long long src_at(const Dims &D, long long f, int g, int h0, int w0) {
     return ((((f * 4 + g) * D.H0 + h0) * D.pitch0) + w0) * 16;
 }
@@ -131,11 +112,9 @@ __global__ __launch_bounds__(kThreads) void updgrad_kernel(const float *__restri
     }
 
     for (long long tile = t0; tile < t1; ++tile) {
-        const int tw = (int)(tile % D.tiles_w);
-        const long long r1 = tile / D.tiles_w;
-        const int th = (int)(r1 % D.tiles_h);
-        const long long f = r1 / D.tiles_h;          // frame b L + l
-        const int l = (int)(f % D.L), h0 = th * kTileH, w0 = tw * kTileW;
+        const TileAt ta = tile_at(D, tile);
+        const long long f = ta.f;
+        const int l = ta.l, h0 = ta.h0, w0 = ta.w0, tw = ta.tw;
 
         __syncthreads();                             // the previous tile's partials have been read
         if (doC) {
@@ -148,7 +127,7 @@ __global__ __launch_bounds__(kThreads) void updgrad_kernel(const float *__restri
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (ll >= 0 && ll < D.L && h >= 0 && h < D.H && w >= 0 && w < D.W) {
-                    const long long at = c16_at(D, f + dt - 1, g, h, w);
+                    const long long at = c16_at(D, 2, f + dt - 1, g, h, w);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float4 *>(g1 + at + q * 4);
                 }
@@ -168,7 +147,7 @@ __global__ __launch_bounds__(kThreads) void updgrad_kernel(const float *__restri
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if (h < D.H && w < D.W) {
-                const long long at = c16_at(D, f, g, h, w);
+                const long long at = c16_at(D, 2, f, g, h, w);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float4 *>(gd + at + q * 4);
             }
@@ -188,7 +167,7 @@ __global__ __launch_bounds__(kThreads) void updgrad_kernel(const float *__restri
                 for (long long i = t; i < n; i += kThreads) {
                     const int piece = (int)(i & 3), col = (int)((i >> 2) % pad), rg = (int)((i >> 2) / pad), g = rg & 1, h = h0 + (rg >> 1);
                     if (h >= D.H) continue;
-                    *reinterpret_cast<float4 *>(d_x1 + c16_at(D, f, g, h, D.W + col) + piece * 4) = zero;
+                    *reinterpret_cast<float4 *>(d_x1 + c16_at(D, 2, f, g, h, D.W + col) + piece * 4) = zero;
                 }
             } else {
                 const int pad = D.pitch0 - D.W0;
@@ -252,7 +231,7 @@ __global__ __launch_bounds__(kThreads) void updgrad_kernel(const float *__restri
                 const int i = t + k * kThreads, piece = i & 3, rest = i >> 2, p = rest % kTile, g = rest / kTile;
                 const int h = h0 + p / kTileW, w = w0 + p % kTileW;
                 if (h < D.H && w < D.W)
-                    *reinterpret_cast<float4 *>(d_x1 + c16_at(D, f, g, h, w) + piece * 4) = wave_sum(sP + p * kPos + g * 16 + piece * 4);
+                    *reinterpret_cast<float4 *>(d_x1 + c16_at(D, 2, f, g, h, w) + piece * 4) = wave_sum(sP + p * kPos + g * 16 + piece * 4);
             }
         } else {
             // source pixel (h0 / 2, w0 / 2 + col): its output positions are rows h0, h0 + 1 and columns w0 + 2 col, + 1
@@ -272,18 +251,8 @@ __global__ __launch_bounds__(kThreads) void updgrad_kernel(const float *__restri
 }
 
 bool make_dims(int B, int L, int H, int W, int pitch, int pitch0, int max_workgroups, Dims &D) {
-    if (B < 1 || L < 1 || H < 1 || W < 1 || pitch < W || max_workgroups < 0) return false;
-    const int H0 = (H - 1) / 2 + 1, W0 = (W - 1) / 2 + 1;
-    if (pitch0 < W0) return false;
-    const long long N = (long long)B * L * H * W;
-    if ((long long)B * L >= (1ll << 31) || (long long)H * W >= (1ll << 31) || N >= (1ll << 31)) return false;
-    if ((long long)B * L * H >= (1ll << 34) || (long long)B * L * H * pitch >= (1ll << 34)) return false;
-    if ((long long)B * L * H0 * pitch0 >= (1ll << 34)) return false;
-    D.B = B; D.L = L; D.H = H; D.W = W; D.pitch = pitch; D.H0 = H0; D.W0 = W0; D.pitch0 = pitch0;
-    D.tiles_h = (H + kTileH - 1) / kTileH;
-    D.tiles_w = (W + kTileW - 1) / kTileW;
-    D.tiles = (long long)B * L * D.tiles_h * D.tiles_w;
-    D.total = ((size_t)kWeights * sizeof(float) + 255) & ~(size_t)255;     // the repacked weights; the grid needs nothing
+    if (!make_extent(B, L, H, W, pitch, true, pitch0, max_workgroups, D)) return false;
+    D.total = round256((size_t)kWeights * sizeof(float));                   // the repacked weights; the grid needs nothing
     return true;
 }
 
@@ -315,15 +284,10 @@ extern "C" int v2ce_convup_dgrad(const float *weight, const float *short_weight,
     V2CE_REQUIRE(aligned16(g1, gd, d_x0, d_x1), V2CE_ERR_BAD_ARG, "v2ce_convup_dgrad: g1, gd, d_x0 and d_x1 must be 16-byte aligned");
     V2CE_REQUIRE(((reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(short_weight)) & 3) == 0, V2CE_ERR_BAD_ARG,
                  "v2ce_convup_dgrad: weight and short_weight must be 4-byte aligned");
-    V2CE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, V2CE_ERR_BAD_ARG,
-                 "v2ce_convup_dgrad: workspace must be 8-byte aligned");
-    V2CE_REQUIRE(workspace_bytes >= D.total, V2CE_ERR_WORKSPACE, "v2ce_convup_dgrad: workspace too small (%zu < %zu)",
-                 workspace_bytes, D.total);
+    if (const int rc = check_workspace("v2ce_convup_dgrad", workspace, workspace_bytes, D.total)) return rc;
     // the requested 32-channel groups of X: 0, 1 (d_x0) and 2 (d_x1)
     const int grp0 = d_x0 ? 0 : 2, ngrp = (d_x0 ? 2 : 0) + (d_x1 ? 1 : 0);
-    long long shares = D.tiles < kMaxGrid / ngrp ? D.tiles : kMaxGrid / ngrp;
-    const long long cap = max_workgroups / ngrp > 0 ? max_workgroups / ngrp : 1;
-    if (max_workgroups > 0 && shares > cap) shares = cap;
+    const int shares = plan_shares(D.tiles, ngrp, max_workgroups);
     hipStream_t st = as_stream(stream);
     float *wt = static_cast<float *>(workspace);
     V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(updgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -1,9 +1,10 @@
 // convupnwgrad.hip -- the weight gradients of a decoder block's first half on gfx950 at any of the decoders' channel counts:
 // the 3x3x3 Conv3d(c0 + c1, cout) conv1 and the 1x1x1 Conv3d(c0 + c1, cout) shortcut, both on the virtual tensor
-// X = cat(nearest_upsample_2x(x0, c0 channels), x1, c1 channels) (include/v2ce_hip_convupngrad.h states the formulas, the
-// tensors and the precision contract).  UNet.decoders[2] is 128 + 64 -> 64; 64 + 32 -> 32 is convupgrad.hip's layer.
+// X = cat(nearest_upsample_2x(x0, c0 channels), x1, c1 channels) (include/v2ce_hip_convupngrad.h and, for the 64 + 32 -> 32
+// entry v2ce_convup_wgrad, include/v2ce_hip_convupgrad.h state the formulas, the tensors and the precision contract).
+// UNet.decoders[3] is 64 + 32 -> 32, UNet.decoders[2] 128 + 64 -> 64.
 //
-// The tile is convupgrad.hip's, run once per pair of a 32-channel group of the outputs and a 32-channel group of X: d_weight
+// The tile is convnwgrad.hip's, run once per pair of a 32-channel group of the outputs and a 32-channel group of X: d_weight
 // is (cout / 32) x ((c0 + c1) / 32) blocks of a 32 x 864 GEMM and d_short as many 32 x 32 GEMMs whose K runs over every
 // output position; v_mfma_f32_32x32x2_f32 takes two positions per instruction: lane l holds A[co = l & 31][k = l >> 5] and
 // B[k = l >> 5][ci = l & 31], so with both operands staged in LDS as [position][32 channels] a wave's A operand of the position
@@ -12,8 +13,8 @@
 //
 // The grid is pairs x shares: workgroup s * pairs + p walks share s of the tiles for pair p = cog * gx + xg, the output
 // channels 32 cog .. + 31 (planes 2 cog, 2 cog + 1 of g1 and gd) against group xg of X (xg < c0 / 32: channels 32 xg .. of x0,
-// read at (h >> 1, w >> 1); the others: channels 32 (xg - c0 / 32) .. of x1).  A tile is 2 rows x 64 columns of one frame
-// (kTile = 128 positions).  Per tile the workgroup stages
+// read at (h >> 1, w >> 1); the others: channels 32 (xg - c0 / 32) .. of x1); 64 + 32 -> 32 has three pairs, all of cog = 0.
+// A tile is 2 rows x 64 columns of one frame (kTile = 128 positions, convgrad_dev.h).  Per tile the workgroup stages
 //   sG  g1 of the tile and its co group, [128][32] f32 (16 KB); positions outside the tensor hold zeros
 //   sD  gd of the tile, the same
 //   sX  the halo of its group of X, 3 frames x 4 rows x 66 columns, [792][32] f32 (99 KB); positions outside the frame, the
@@ -22,7 +23,7 @@
 // and wave v takes the units 7 v .. 7 v + 6 of 28: unit u < 27 is tap u of d_weight (A from sG), unit 27 -- the last wave's
 // seventh -- is d_short: A from sD, B at the centre tap's halo offset, so the staged halo serves both layers.  Per position
 // pair two reads for A and one read of sX per unit feed one MFMA per unit, 7 x 16 accumulator registers per lane.  A
-// workgroup stages 32 channels of every tensor at a time, so the LDS budget and the bank arguments are convupgrad.hip's.
+// workgroup stages 32 channels of every tensor at a time, whatever the channel counts are.
 //
 // Chain and flush: an f32 accumulator takes kChainTiles = V2CE_UPWGRAD_CHAIN / 128 tiles; then (and after the last tile) the
 // lane that owns it adds it into the workgroup's f64 partial in the workspace (the first flush stores) and clears it.  A
@@ -30,63 +31,33 @@
 // sums channel t & 31 over the 16 positions (t >> 5) * 16 .. + 15 of sD in f64, tile after tile; the eight sums of a channel
 // meet at the end in a fixed order.  finish_kernel: one thread per output adds its pair's partials in the order of the shares
 // 0 .. shares - 1 and rounds once.  A unit's arithmetic does not depend on which other units run: an output's bytes do not
-// depend on which others were asked for.  At 64 + 32 -> 32 (three pairs, cog = 0) every step is convupgrad.hip's.
-#include "common.h"
+// depend on which others were asked for.
+#include "convgrad_dev.h"
 
 #include "../../include/v2ce_hip_convupngrad.h"
 
 namespace v2ce {
 namespace {
 
-constexpr int kThreads = 256;                       // 4 waves
-constexpr int kC = 32;                              // channels of a group on either side
-constexpr int kTaps = 27;
 constexpr int kUnits = kTaps + 1;                   // 27 taps of d_weight and d_short
 constexpr int kUnitsPerWave = 7;
-constexpr int kTileH = 2, kTileW = 64, kTile = kTileH * kTileW;
-constexpr int kHaloT = 3, kHaloH = kTileH + 2, kHaloW = kTileW + 2;
-constexpr int kHalo = kHaloT * kHaloH * kHaloW;     // 792 positions
 constexpr int kCentre = ((1 * kHaloH + 1) * kHaloW + 1) * kC;   // float offset of the tap (1, 1, 1) inside sX
 constexpr int kChainTiles = V2CE_UPWGRAD_CHAIN / kTile;
-constexpr int kMaxGrid = 256;                       // one workgroup per CU: 131 KB of LDS each
 constexpr int kPartial = kUnits * kC * kC + kC;     // f64 per workgroup: [28][32][32] unit blocks, [32] d_short_bias (xg = 0)
-constexpr size_t kLds = (size_t)(2 * kTile + kHalo) * kC * sizeof(float);
+constexpr size_t kLds = (size_t)(2 * kTile + kHalo) * kC * sizeof(float);       // 131 KB
 static_assert(kUnits == 4 * kUnitsPerWave, "every wave owns seven units");
 static_assert(kChainTiles >= 1 && kChainTiles * kTile <= V2CE_UPWGRAD_CHAIN && V2CE_UPWGRAD_CHAIN <= 4096, "chain length");
 static_assert(kLds <= 160 * 1024, "LDS of one workgroup");
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct Dims {
-    int B, L, H, W, pitch, H0, W0, pitch0;
+struct Dims : Extent {
     int c0, c1, cout, g0, gx, pairs;                // g0: groups of 32 channels of x0; gx: of X; pairs = (cout / 32) gx
-    int tiles_h, tiles_w;
-    long long tiles;                                // B L tiles_h tiles_w
     int shares;
     size_t total;
 };
 
-// float offset of plane g (16 channels) of (frame, row, column) in a C16 tensor with `planes` planes at the output resolution
-__device__ __forceinline__ long long c16_at(const Dims &D, int planes, long long f, int g, int h, int w) {
-    return ((((f * planes + g) * D.H + h) * D.pitch) + w) * 16;
-}
-
-// the same in the source x0 of the upsampled channels, (h, w) at the output resolution
+// c16_at in the source x0 of the upsampled channels, (h, w) at the output resolution
 __device__ __forceinline__ long long up_at(const Dims &D, int planes, long long f, int g, int h, int w) {
     return ((((f * planes + g) * D.H0 + (h >> 1)) * D.pitch0) + (w >> 1)) * 16;
-}
-
-// a [128][32] tile of planes 2 cog, 2 cog + 1 of g1 or gd into LDS; positions outside the tensor hold zeros
-__device__ __forceinline__ void stage_tile(const Dims &D, const float *__restrict__ src, float *dst, int planes, int cog,
-                                           long long f, int h0, int w0, int t) {
-#pragma unroll
-    for (int k = 0; k < kTile * 8 / kThreads; ++k) {
-        const int i = t + k * kThreads, piece = i & 3, rest = i >> 2, g = rest / kTile, p = rest % kTile;
-        const int h = h0 + p / kTileW, w = w0 + p % kTileW;
-        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (h < D.H && w < D.W) v = *reinterpret_cast<const float4 *>(src + c16_at(D, planes, f, cog * 2 + g, h, w) + piece * 4);
-        *reinterpret_cast<float4 *>(dst + p * kC + g * 16 + piece * 4) = v;
-    }
 }
 
 __global__ __launch_bounds__(kThreads) void upnwgrad_kernel(const float *__restrict__ x0, const float *__restrict__ x1,
@@ -127,15 +98,13 @@ __global__ __launch_bounds__(kThreads) void upnwgrad_kernel(const float *__restr
     bool stored = false;
 
     for (long long tile = t0; tile < t1; ++tile) {
-        const int tw = (int)(tile % D.tiles_w);
-        const long long r1 = tile / D.tiles_w;
-        const int th = (int)(r1 % D.tiles_h);
-        const long long f = r1 / D.tiles_h;          // frame b L + l
-        const int l = (int)(f % D.L), h0 = th * kTileH, w0 = tw * kTileW;
+        const TileAt ta = tile_at(D, tile);
+        const long long f = ta.f;
+        const int l = ta.l, h0 = ta.h0, w0 = ta.w0;
 
         __syncthreads();                             // the previous tile has been read
-        if (doW) stage_tile(D, g1, sG, gplanes, cog, f, h0, w0, t);
-        if (doS || doB) stage_tile(D, gd, sD, gplanes, cog, f, h0, w0, t);
+        if (doW) stage_tile(D, g1, nullptr, sG, gplanes, cog * 2, f, h0, w0, t);
+        if (doS || doB) stage_tile(D, gd, nullptr, sD, gplanes, cog * 2, f, h0, w0, t);
         if (doX) {
             // the halo of this group of X: 792 positions x 8 pieces
 #pragma unroll 5
@@ -178,11 +147,7 @@ __global__ __launch_bounds__(kThreads) void upnwgrad_kernel(const float *__restr
                 }
             }
         }
-        if (doB) {
-            const float *row = sD + (t >> 5) * 16 * kC + (t & 31);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) bsum += (double)row[i * kC];
-        }
+        if (doB) add_channel_part(sD, t, bsum);
 
         if (doX && (++chain == kChainTiles || tile + 1 == t1)) {
             // C/D map of the 32x32 MFMA: column (ci) = lane & 31, row (co) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
@@ -205,19 +170,7 @@ __global__ __launch_bounds__(kThreads) void upnwgrad_kernel(const float *__restr
         }
     }
 
-    if (doB) {
-        // channel t & 31: parts 2 wv (lanes 0 .. 31) and 2 wv + 1 (lanes 32 .. 63); summed in the order of the parts
-        double *red = reinterpret_cast<double *>(smem);
-        __syncthreads();
-        red[t] = bsum;
-        __syncthreads();
-        if (t < kC) {
-            double s = red[t];
-#pragma unroll
-            for (int part = 1; part < kThreads / kC; ++part) s += red[part * kC + t];
-            mine[kUnits * kC * kC + t] = s;
-        }
-    }
+    if (doB) reduce_channel_parts(reinterpret_cast<double *>(smem), t, bsum, mine + kUnits * kC * kC);
 }
 
 // one thread per output: e < pairs * 28 * 1024 is (pair, unit, co, ci) of d_weight (unit < 27) or d_short, the others
@@ -249,29 +202,44 @@ __global__ __launch_bounds__(kThreads) void upnwgrad_finish_kernel(const double 
 
 bool make_dims(int c0, int c1, int cout, int B, int L, int H, int W, int pitch, int pitch0, int max_workgroups, Dims &D) {
     if ((c0 != 64 && c0 != 128) || (c1 != 32 && c1 != 64) || (cout != 32 && cout != 64)) return false;
-    if (B < 1 || L < 1 || H < 1 || W < 1 || pitch < W || max_workgroups < 0) return false;
-    const int H0 = (H - 1) / 2 + 1, W0 = (W - 1) / 2 + 1;
-    if (pitch0 < W0) return false;
-    const long long N = (long long)B * L * H * W;
-    if ((long long)B * L >= (1ll << 31) || (long long)H * W >= (1ll << 31) || N >= (1ll << 31)) return false;
-    if ((long long)B * L * H >= (1ll << 34) || (long long)B * L * H * pitch >= (1ll << 34)) return false;
-    if ((long long)B * L * H0 * pitch0 >= (1ll << 34)) return false;
-    D.B = B; D.L = L; D.H = H; D.W = W; D.pitch = pitch; D.H0 = H0; D.W0 = W0; D.pitch0 = pitch0;
+    if (!make_extent(B, L, H, W, pitch, true, pitch0, max_workgroups, D)) return false;
     D.c0 = c0; D.c1 = c1; D.cout = cout; D.g0 = c0 / kC; D.gx = (c0 + c1) / kC; D.pairs = (cout / kC) * D.gx;
-    D.tiles_h = (H + kTileH - 1) / kTileH;
-    D.tiles_w = (W + kTileW - 1) / kTileW;
-    D.tiles = (long long)B * L * D.tiles_h * D.tiles_w;
-    const long long most = kMaxGrid / D.pairs;
-    long long shares = D.tiles < most ? D.tiles : most;
-    const long long cap = max_workgroups / D.pairs > 1 ? max_workgroups / D.pairs : 1;
-    if (max_workgroups > 0 && shares > cap) shares = cap;
-    D.shares = (int)shares;
-    D.total = (((size_t)D.shares * D.pairs * kPartial * sizeof(double)) + 255) & ~(size_t)255;
+    D.shares = plan_shares(D.tiles, D.pairs, max_workgroups);
+    D.total = round256((size_t)D.shares * D.pairs * kPartial * sizeof(double));
     return true;
 }
 
 const char *kNeeds = "needs c0 in {64, 128}, c1 and cout in {32, 64}, B, L, H, W >= 1, pitch >= W, pitch0 >= (W + 1) / 2, "
                      "max_workgroups >= 0, B L H W < 2^31, B L H pitch < 2^34 and B L H0 pitch0 < 2^34";
+
+// `entry`: the symbol the caller used; it leads every message
+int upnwgrad(const char *entry, const float *x0, const float *x1, const float *g1, const float *gd, int c0, int c1, int cout, int B,
+             int L, int H, int W, int pitch, int pitch0, float *d_weight, float *d_short, float *d_short_bias, void *workspace,
+             size_t workspace_bytes, int max_workgroups, v2ce_stream_t stream) {
+    clear_error();
+    Dims D;
+    V2CE_REQUIRE(make_dims(c0, c1, cout, B, L, H, W, pitch, pitch0, max_workgroups, D), V2CE_ERR_BAD_ARG,
+                 "%s: c0 %d c1 %d cout %d B %d L %d H %d W %d pitch %d pitch0 %d max_workgroups %d: %s", entry, c0, c1, cout, B, L, H,
+                 W, pitch, pitch0, max_workgroups, kNeeds);
+    V2CE_REQUIRE(d_weight || d_short || d_short_bias, V2CE_ERR_BAD_ARG,
+                 "%s: no output requested (d_weight, d_short and d_short_bias are all null)", entry);
+    const int doW = d_weight != nullptr, doS = d_short != nullptr, doB = d_short_bias != nullptr;
+    V2CE_REQUIRE(workspace && (!(doW || doS) || (x0 && x1)) && (!doW || g1) && (!(doS || doB) || gd), V2CE_ERR_BAD_ARG,
+                 "%s: null pointer (d_weight needs x0, x1 and g1; d_short x0, x1 and gd; d_short_bias gd)", entry);
+    V2CE_REQUIRE(aligned16(x0, x1, g1, gd), V2CE_ERR_BAD_ARG, "%s: x0, x1, g1 and gd must be 16-byte aligned", entry);
+    if (const int rc = check_workspace(entry, workspace, workspace_bytes, D.total)) return rc;
+    hipStream_t st = as_stream(stream);
+    double *partial = static_cast<double *>(workspace);
+    const int outputs = D.pairs * kUnits * kC * kC + D.cout;
+    V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(upnwgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)kLds));
+    hipLaunchKernelGGL(upnwgrad_kernel, dim3((unsigned)(D.shares * D.pairs)), dim3(kThreads), kLds, st, x0, x1, g1, gd, D, doW, doS,
+                       doB, partial);
+    hipLaunchKernelGGL(upnwgrad_finish_kernel, dim3((outputs + kThreads - 1) / kThreads), dim3(kThreads), 0, st, partial, D, doW,
+                       doS, doB, d_weight, d_short, d_short_bias);
+    V2CE_HIP_CHECK(hipGetLastError());
+    return V2CE_OK;
+}
 
 }  // namespace
 }  // namespace v2ce
@@ -287,30 +255,18 @@ extern "C" size_t v2ce_convupn_wgrad_workspace_bytes(int c0, int c1, int cout, i
 extern "C" int v2ce_convupn_wgrad(const float *x0, const float *x1, const float *g1, const float *gd, int c0, int c1, int cout, int B,
                                   int L, int H, int W, int pitch, int pitch0, float *d_weight, float *d_short, float *d_short_bias,
                                   void *workspace, size_t workspace_bytes, int max_workgroups, v2ce_stream_t stream) {
-    clear_error();
-    Dims D;
-    V2CE_REQUIRE(make_dims(c0, c1, cout, B, L, H, W, pitch, pitch0, max_workgroups, D), V2CE_ERR_BAD_ARG,
-                 "v2ce_convupn_wgrad: c0 %d c1 %d cout %d B %d L %d H %d W %d pitch %d pitch0 %d max_workgroups %d: %s", c0, c1, cout,
-                 B, L, H, W, pitch, pitch0, max_workgroups, kNeeds);
-    V2CE_REQUIRE(d_weight || d_short || d_short_bias, V2CE_ERR_BAD_ARG,
-                 "v2ce_convupn_wgrad: no output requested (d_weight, d_short and d_short_bias are all null)");
-    const int doW = d_weight != nullptr, doS = d_short != nullptr, doB = d_short_bias != nullptr;
-    V2CE_REQUIRE(workspace && (!(doW || doS) || (x0 && x1)) && (!doW || g1) && (!(doS || doB) || gd), V2CE_ERR_BAD_ARG,
-                 "v2ce_convupn_wgrad: null pointer (d_weight needs x0, x1 and g1; d_short x0, x1 and gd; d_short_bias gd)");
-    V2CE_REQUIRE(aligned16(x0, x1, g1, gd), V2CE_ERR_BAD_ARG, "v2ce_convupn_wgrad: x0, x1, g1 and gd must be 16-byte aligned");
-    V2CE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, V2CE_ERR_BAD_ARG,
-                 "v2ce_convupn_wgrad: workspace must be 8-byte aligned");
-    V2CE_REQUIRE(workspace_bytes >= D.total, V2CE_ERR_WORKSPACE, "v2ce_convupn_wgrad: workspace too small (%zu < %zu)",
-                 workspace_bytes, D.total);
-    hipStream_t st = as_stream(stream);
-    double *partial = static_cast<double *>(workspace);
-    const int outputs = D.pairs * kUnits * kC * kC + D.cout;
-    V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(upnwgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)kLds));
-    hipLaunchKernelGGL(upnwgrad_kernel, dim3((unsigned)(D.shares * D.pairs)), dim3(kThreads), kLds, st, x0, x1, g1, gd, D, doW, doS,
-                       doB, partial);
-    hipLaunchKernelGGL(upnwgrad_finish_kernel, dim3((outputs + kThreads - 1) / kThreads), dim3(kThreads), 0, st, partial, D, doW,
-                       doS, doB, d_weight, d_short, d_short_bias);
-    V2CE_HIP_CHECK(hipGetLastError());
-    return V2CE_OK;
+    return upnwgrad("v2ce_convupn_wgrad", x0, x1, g1, gd, c0, c1, cout, B, L, H, W, pitch, pitch0, d_weight, d_short, d_short_bias,
+                    workspace, workspace_bytes, max_workgroups, stream);
+}
+
+// the 64 + 32 -> 32 entries of include/v2ce_hip_convupgrad.h: three pairs, 85 shares at the most
+extern "C" size_t v2ce_convup_wgrad_workspace_bytes(int B, int L, int H, int W, int pitch, int pitch0, int max_workgroups) {
+    return v2ce_convupn_wgrad_workspace_bytes(64, 32, 32, B, L, H, W, pitch, pitch0, max_workgroups);
+}
+
+extern "C" int v2ce_convup_wgrad(const float *x0, const float *x1, const float *g1, const float *gd, int B, int L, int H, int W,
+                                 int pitch, int pitch0, float *d_weight, float *d_short, float *d_short_bias, void *workspace,
+                                 size_t workspace_bytes, int max_workgroups, v2ce_stream_t stream) {
+    return upnwgrad("v2ce_convup_wgrad", x0, x1, g1, gd, 64, 32, 32, B, L, H, W, pitch, pitch0, d_weight, d_short, d_short_bias,
+                    workspace, workspace_bytes, max_workgroups, stream);
 }

@@ -1,6 +1,6 @@
 """The first half of the last decoder block -- the spectral-normalised 3x3x3 ``conv1`` and the 1x1x1 shortcut convolution
 ``downsample.0`` of ``UNet.decoders[3]``, both ``Conv3d(96, 32)`` on ``cat(nearest_upsample_2x(dec2 output), skip)`` -- as
-trainable layers on the GPU (include/v2ce_hip_convupgrad.h, csrc/convupgrad.hip).
+trainable layers on the GPU (include/v2ce_hip_convupgrad.h, csrc/convupnwgrad.hip).
 
     x0, x1 = model.forward_tail_sources(x)        # the frozen trunk up to the block's two sources, no gradient
     convs = TailConvs.from_model(model)           # weight_bar [32, 96, 3, 3, 3], short_weight [32, 96, 1, 1, 1], short_bias

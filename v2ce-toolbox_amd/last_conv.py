@@ -1,5 +1,5 @@
 """The last decoder convolution ``UNet.decoders[3].conv2`` as a trainable layer on the GPU (include/v2ce_hip_convgrad.h,
-csrc/convgrad.hip; include/v2ce_hip_convdgrad.h, csrc/convdgrad.hip).
+csrc/convnwgrad.hip; include/v2ce_hip_convdgrad.h, csrc/convndgrad.hip).
 
 In the reference it is the second convolution of ``ResidualBlock3D(96, 32, norm='BN', sn=True)``: a spectral-normalised
 3x3x3 ``Conv3d(32, 32)`` followed by ``bn2``, the shortcut add and ``relu`` (train/scripts/model/submodules.py:210-258,
