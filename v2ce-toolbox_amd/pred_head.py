@@ -48,18 +48,25 @@ def _check_f32(t, name, device=None):
         raise ValueError(f"{name} lives on {t.device}, feat on {device}")
 
 
-def _check_feat(feat, name="feat"):
-    """-> (B, L, H, W, pitch) of a channels-last-16 feature tensor."""
-    _check_f32(feat, name)
-    if feat.dim() != 6 or feat.shape[2] != 2 or feat.shape[5] != 16:
-        raise ValueError(f"{name} must be channels-last-16 [b, l, 2, h, pitch, 16], got {tuple(getattr(feat, 'shape', ()))}")
-    B, L, _, H, pitch, _ = (int(v) for v in feat.shape)
-    W = int(getattr(feat, "lw", pitch))
+def _check_c16(t, name, channels):
+    """-> (C, B, L, H, W, pitch) of a channels-last-16 tensor whose channel count is one of ``channels``: the one shape
+    check of the head, the gradient entries (conv_grads.py) and the trainable layers (decoder_block.py)."""
+    _check_f32(t, name)
+    if t.dim() != 6 or t.shape[5] != 16 or int(t.shape[2]) * 16 not in channels:
+        raise ValueError(f"{name} must be channels-last-16 [b, l, c / 16, h, pitch, 16] with c in {tuple(channels)}, got "
+                         f"{tuple(getattr(t, 'shape', ()))}")
+    B, L, G, H, pitch, _ = (int(v) for v in t.shape)
+    W = int(getattr(t, "lw", pitch))
     if not 1 <= W <= pitch:
         raise ValueError(f"{name}.lw = {W} is outside 1 .. pitch = {pitch}")
-    if feat.data_ptr() % 16:
+    if t.data_ptr() % 16:
         raise ValueError(f"{name} must be 16-byte aligned")
-    return B, L, H, W, pitch
+    return G * 16, B, L, H, W, pitch
+
+
+def _check_feat(feat, name="feat"):
+    """-> (B, L, H, W, pitch) of a channels-last-16 feature tensor."""
+    return _check_c16(feat, name, (CIN,))[1:]
 
 
 def _check_weight(weight, device):
