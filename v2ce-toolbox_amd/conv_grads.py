@@ -1,13 +1,14 @@
 """The checked Python entries of the convolution gradient kernels the trainable decoder layers stand on
 (include/v2ce_hip_convgrad.h, v2ce_hip_convdgrad.h, v2ce_hip_convupgrad.h, v2ce_hip_convupdgrad.h, v2ce_hip_convngrad.h,
-v2ce_hip_convupngrad.h; csrc/convnwgrad.hip, convndgrad.hip, convupnwgrad.hip, convupdgrad.hip):
+v2ce_hip_convupngrad.h, v2ce_hip_convupndgrad.h; csrc/convnwgrad.hip, convndgrad.hip, convupnwgrad.hip, convupdgrad.hip):
 
     convn_wgrad / convn_dgrad    a stride-1 3x3x3 convolution cin -> cout seen through the relu behind it
     convupn_wgrad                the 3x3x3 and the 1x1x1 convolution c0 + c1 -> cout on cat(nearest_upsample_2x(x0), x1)
-    convup_dgrad                 the input gradients of that pair, at 64 + 32 -> 32 only
-    conv32_wgrad / conv32_dgrad / convup_wgrad
-                                 the first three with the channel counts fixed at 32 -> 32 and 64 + 32 -> 32, through C
-                                 entries of their own (v2ce_conv32_wgrad, v2ce_conv32_dgrad, v2ce_convup_wgrad)
+    convupn_dgrad                the input gradients of that pair, back through the concat and the upsample
+    conv32_wgrad / conv32_dgrad / convup_wgrad / convup_dgrad
+                                 the same four with the channel counts fixed at 32 -> 32 and 64 + 32 -> 32, through C
+                                 entries of their own (v2ce_conv32_wgrad, v2ce_conv32_dgrad, v2ce_convup_wgrad,
+                                 v2ce_convup_dgrad)
 
 Every entry validates its tensors (``pred_head._check_c16``: channels-last-16 f32 on the device, ``.lw`` inside the pitch,
 16-byte aligned), ``want`` / ``out`` / ``max_workgroups``, refuses an output that overlaps an input, queries the workspace
@@ -28,7 +29,7 @@ WGRAD_WANT = ("weight", "shift")
 DGRAD_WANT = ("x", "res")
 UPWGRAD_WANT = ("weight", "short", "short_bias")
 UPDGRAD_WANT = ("x0", "x1")
-UP_C0, UP_C1, UP_COUT = 64, 32, 32         # the one channel triple of convup_dgrad
+UP_C0, UP_C1, UP_COUT = 64, 32, 32         # the one channel triple of convup_wgrad and convup_dgrad
 
 
 class _Entry(NamedTuple):
@@ -46,6 +47,7 @@ _CONV32_DGRAD = _Entry("v2ce_conv32_dgrad", ((32,), (32,)), False)
 _CONVUPN_WGRAD = _Entry("v2ce_convupn_wgrad", (hip.CONVUPN_C0, hip.CONVUPN_C1, hip.CONVUPN_COUT), True)
 _CONVUP_WGRAD = _Entry("v2ce_convup_wgrad", ((UP_C0,), (UP_C1,), (UP_COUT,)), False)
 _CONVUP_DGRAD = _Entry("v2ce_convup_dgrad", ((UP_C0,), (UP_C1,), (UP_COUT,)), False)
+_CONVUPN_DGRAD = _Entry("v2ce_convupn_dgrad", (hip.CONVUPN_C0, hip.CONVUPN_C1, hip.CONVUPN_COUT), True)
 
 
 def check_sources(x0, x1, c0s=hip.CONVUPN_C0, c1s=hip.CONVUPN_C1):
@@ -273,24 +275,29 @@ def convup_wgrad(x0: torch.Tensor, x1: torch.Tensor, g1: Optional[torch.Tensor],
     return _upwgrad(_CONVUP_WGRAD, x0, x1, g1, gd, want, out, max_workgroups)
 
 
-def convup_dgrad(weight: Optional[torch.Tensor], short_weight: Optional[torch.Tensor], g1: Optional[torch.Tensor],
-                 gd: Optional[torch.Tensor], *, want: Sequence[str] = UPDGRAD_WANT, out: Optional[dict] = None,
-                 max_workgroups: int = 0) -> dict:
-    """The gradients of the 3x3x3 and the 1x1x1 convolution 96 -> 32 on the virtual tensor
-    ``X = cat(nearest_upsample_2x(x0), x1)`` with respect to ``x0`` and ``x1``.  ``weight`` is the 3x3x3 convolution's own
-    contiguous ``[32, 96, 3, 3, 3]`` f32 weight, ``short_weight`` the 1x1x1 convolution's ``[32, 96]`` (or
-    ``[32, 96, 1, 1, 1]``); ``g1`` (the gradient with respect to the 3x3x3 convolution's output) and ``gd`` (the gradient
-    with respect to the 1x1x1 convolution's output) are channels-last-16 ``[B, L, 2, H, pitch, 16]`` f32 with the same shape
-    and ``.lw``.  ``g1`` may be None (``weight`` is then unused): the 1x1x1 convolution's share alone; ``gd`` may be None
-    (``short_weight`` likewise); not both.
-    -> {name: tensor} for the names in ``want`` (a subset of 'x0', 'x1'): 'x1' ``[B, L, 2, H, pitch, 16]`` = the last 32
-    channels of d_X = conv_transpose(g1, weight) + short_weight^T gd, 'x0' ``[B, L, 4, H0, pitch0, 16]`` with
-    ``H0 = (H + 1) // 2``, ``.lw = (W + 1) // 2`` and ``pitch0 = V2ce3d._pitch(.lw)`` (or that of ``out['x0']``) = the first
-    64 channels summed over the output positions of each source pixel.  Both carry ``.lw`` and ``.c16``; their padding
-    columns are zeros.  ``out``: {name: tensor} to write into.  ``max_workgroups``: 0 = the kernel's choice, n > 0 caps the
-    grid (the bytes do not depend on n).  One call, no host synchronisation."""
+def _resolve_c0(entry, cin, given, c0):
+    """How the cin input channels of a weight split into c0 + c1: from out['x0'] (``given``) where it is there, else from
+    ``c0``, else from cin alone.  cin alone does not say it where cin is itself one of the entry's c0: 128 input channels
+    are 64 + 64, or the 128 channels of an x0 with no skip tensor beside it, which no entry takes -- a caller who means the
+    second must hear so and not get the first's gradients.  -> c0, or None where cin is no sum the entry takes."""
+    pairs = [(a, b) for a in entry.channels[0] for b in entry.channels[1] if a + b == cin]
+    if not pairs:
+        return None
+    if c0 is None and given is not None and given.dim() == 6:
+        c0 = 16 * int(given.shape[2])
+    if c0 is None:
+        if cin in entry.channels[0]:
+            raise ValueError(f"a weight with {cin} input channels reads as {pairs[0][0]} + {pairs[0][1]} or as {cin} + 0 (which "
+                             f"is refused): say which with c0={pairs[0][0]} or out['x0']")
+        return pairs[0][0]
+    if (int(c0), cin - int(c0)) not in pairs:
+        raise ValueError(f"c0 = {c0} does not split {cin} input channels into c0 in {tuple(entry.channels[0])} and c1 in "
+                         f"{tuple(entry.channels[1])}")
+    return int(c0)
+
+
+def _updgrad(entry, weight, short_weight, g1, gd, want, out, max_workgroups, c0=None):
     from .v2ce_3d import V2ce3d
-    entry = _CONVUP_DGRAD
     want, cap = _arguments(want, UPDGRAD_WANT, max_workgroups)
     if g1 is None and gd is None:
         raise ValueError("g1 and gd are both None")
@@ -298,39 +305,79 @@ def convup_dgrad(weight: Optional[torch.Tensor], short_weight: Optional[torch.Te
         raise ValueError("g1 needs weight")
     if gd is not None and short_weight is None:
         raise ValueError("gd needs short_weight")
+    given = (out or {}).get("x0")
+    first = weight if g1 is not None else short_weight
+    cin = int(first.shape[1]) if first.dim() >= 2 else 0
+    c0 = _resolve_c0(entry, cin, given, c0)          # an ambiguous call is refused before anything else is looked at
     lead, lead_name = (g1, "g1") if g1 is not None else (gd, "gd")
-    _, B, L, H, W, pitch = _check_c16(lead, lead_name, entry.channels[2])
+    cout, B, L, H, W, pitch = _check_c16(lead, lead_name, entry.channels[2])
     dev = lead.device
     ins = [(lead_name, lead)]
     if g1 is not None and gd is not None:
         _check_same(gd, "gd", _check_c16(gd, "gd", entry.channels[2])[1:], g1, "g1", (B, L, H, W, pitch))
         ins.append(("gd", gd))
-    C, CIN = UP_COUT, UP_C0 + UP_C1
-    for n, t, ok, used in (("weight", weight, ((C, CIN, 3, 3, 3),), g1 is not None),
-                           ("short_weight", short_weight, ((C, CIN), (C, CIN, 1, 1, 1)), gd is not None)):
+    # the input channels a weight may have: those the call resolved to, or (where it did not) every sum the entry takes
+    cins = (cin,) if c0 is not None else sorted({a + b for a in entry.channels[0] for b in entry.channels[1]})
+    for n, t, tails, used in (("weight", weight, ((3, 3, 3),), g1 is not None),
+                              ("short_weight", short_weight, ((), (1, 1, 1)), gd is not None)):
         if not used:
             continue
         _check_f32(t, n, dev)
+        ok = [(cout, ci) + tail for tail in tails for ci in cins]
         if tuple(t.shape) not in ok:
-            raise ValueError(f"{n} must be {' or '.join(str(list(s)) for s in ok)}, got {tuple(t.shape)}")
+            raise ValueError(f"{n} must be {' or '.join(str(list(sh)) for sh in ok)}, got {tuple(t.shape)}")
         ins.append((n, t))
+    c1 = cin - c0
     _check_half(H, W)
     H0, W0 = (H + 1) // 2, (W + 1) // 2
-    given = (out or {}).get("x0")
+    x1_shape = (B, L, c1 // 16, H, pitch, 16)
 
     def check(n, t):
-        if n == "x1" and tuple(t.shape) != tuple(lead.shape):
-            raise ValueError(f"out['x1'] {tuple(t.shape)} must match {lead_name} {tuple(lead.shape)}")
-        if n == "x0" and (t.dim() != 6 or tuple(t.shape[:4]) != (B, L, UP_C0 // 16, H0) or t.shape[4] < W0 or t.shape[5] != 16):
-            raise ValueError(f"out['x0'] {tuple(t.shape)} must be [{B}, {L}, 4, {H0}, pitch0 >= {W0}, 16]")
+        if n == "x1" and tuple(t.shape) != x1_shape:
+            raise ValueError(f"out['x1'] {tuple(t.shape)} must match {lead_name} {tuple(lead.shape)}" +
+                             (f" with {c1 // 16} planes" if entry.pass_channels else ""))
+        if n == "x0" and (t.dim() != 6 or tuple(t.shape[:4]) != (B, L, c0 // 16, H0) or t.shape[4] < W0 or t.shape[5] != 16):
+            raise ValueError(f"out['x0'] {tuple(t.shape)} must be [{B}, {L}, {c0 // 16}, {H0}, pitch0 >= {W0}, 16]")
         if t.data_ptr() % 16:
             raise ValueError(f"out['{n}'] must be 16-byte aligned")
     out = _outputs(out, want, dev, ins, check)
     pitch0 = int(given.shape[4]) if given is not None else V2ce3d._pitch(W0)
-    shapes = {"x0": (B, L, UP_C0 // 16, H0, pitch0, 16), "x1": tuple(lead.shape)}
-    res = _launch(entry, (), (B, L, H, W, pitch, pitch0), f"pitch {pitch}, pitch0 {pitch0}",
+    shapes = {"x0": (B, L, c0 // 16, H0, pitch0, 16), "x1": x1_shape}
+    detail = f"pitch {pitch}, pitch0 {pitch0}" + (f", {c0} + {c1} -> {cout}" if entry.pass_channels else "")
+    res = _launch(entry, (c0, c1, cout), (B, L, H, W, pitch, pitch0), detail,
                   (hip.ptr(weight) if g1 is not None else None, hip.ptr(short_weight) if gd is not None else None, hip.ptr(g1),
                    hip.ptr(gd)), UPDGRAD_WANT, want, out, shapes, cap, dev)
     for n, t in res.items():
         t.lw, t.c16 = (W0 if n == "x0" else W), True
     return res
+
+
+def convupn_dgrad(weight: Optional[torch.Tensor], short_weight: Optional[torch.Tensor], g1: Optional[torch.Tensor],
+                  gd: Optional[torch.Tensor], *, want: Sequence[str] = UPDGRAD_WANT, out: Optional[dict] = None,
+                  max_workgroups: int = 0, c0: Optional[int] = None) -> dict:
+    """The gradients of the 3x3x3 and the 1x1x1 convolution c0 + c1 -> cout on the virtual tensor
+    ``X = cat(nearest_upsample_2x(x0), x1)`` with respect to ``x0`` and ``x1`` (c0 = 64 or 128, c1 = 32 or 64, cout = 32 or
+    64).  ``weight`` is the 3x3x3 convolution's own contiguous ``[cout, c0 + c1, 3, 3, 3]`` f32 weight, ``short_weight`` the
+    1x1x1 convolution's ``[cout, c0 + c1]`` (or ``[cout, c0 + c1, 1, 1, 1]``); ``g1`` (the gradient with respect to the 3x3x3
+    convolution's output) and ``gd`` (the gradient with respect to the 1x1x1 convolution's output) are channels-last-16
+    ``[B, L, cout / 16, H, pitch, 16]`` f32 with the same shape and ``.lw``.  ``g1`` may be None (``weight`` is then
+    unused): the 1x1x1 convolution's share alone; ``gd`` may be None (``short_weight`` likewise); not both.
+    ``c0``: how the weight's input channels split.  96 is 64 + 32, 160 is 128 + 32 and 192 is 128 + 64, but 128 is 64 + 64
+    or an ``x0`` of 128 channels with nothing beside it: a 128-channel weight is refused unless ``c0`` or ``out['x0']``
+    (whose planes say it) is given.  Elsewhere ``c0`` may be omitted.
+    -> {name: tensor} for the names in ``want`` (a subset of 'x0', 'x1'): 'x1' ``[B, L, c1 / 16, H, pitch, 16]`` = the last
+    c1 channels of d_X = conv_transpose(g1, weight) + short_weight^T gd, 'x0' ``[B, L, c0 / 16, H0, pitch0, 16]`` with
+    ``H0 = (H + 1) // 2``, ``.lw = (W + 1) // 2`` and ``pitch0 = V2ce3d._pitch(.lw)`` (or that of ``out['x0']``) = the first
+    c0 channels summed over the output positions of each source pixel.  Both carry ``.lw`` and ``.c16``; their padding
+    columns are zeros.  ``out``: {name: tensor} to write into.  ``max_workgroups``: 0 = the kernel's choice, n > 0 caps the
+    grid (the bytes do not depend on n).  One call, no host synchronisation."""
+    return _updgrad(_CONVUPN_DGRAD, weight, short_weight, g1, gd, want, out, max_workgroups, c0)
+
+
+def convup_dgrad(weight: Optional[torch.Tensor], short_weight: Optional[torch.Tensor], g1: Optional[torch.Tensor],
+                 gd: Optional[torch.Tensor], *, want: Sequence[str] = UPDGRAD_WANT, out: Optional[dict] = None,
+                 max_workgroups: int = 0) -> dict:
+    """``convupn_dgrad`` at 64 + 32 -> 32 through ``v2ce_convup_dgrad``: ``weight`` is ``[32, 96, 3, 3, 3]``,
+    ``short_weight`` ``[32, 96]`` (or ``[32, 96, 1, 1, 1]``), ``g1``, ``gd`` and 'x1' are ``[B, L, 2, H, pitch, 16]`` and
+    'x0' is ``[B, L, 4, H0, pitch0, 16]``; anything else is refused."""
+    return _updgrad(_CONVUP_DGRAD, weight, short_weight, g1, gd, want, out, max_workgroups)

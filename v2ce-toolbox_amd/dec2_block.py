@@ -1,8 +1,9 @@
 """The first half of the third decoder block -- the spectral-normalised 3x3x3 ``conv1`` and the 1x1x1 shortcut convolution
 ``downsample.0`` of ``UNet.decoders[2]``, both ``Conv3d(192, 64)`` on ``cat(nearest_upsample_2x(dec1 output), skip)``, with
 the affine parts of ``bn1`` / ``downsample.1`` -- as trainable layers on the GPU, the whole block as one layer, and the
-weight gradients through the upsample + concat at any of the decoders' channel counts that they stand on
-(include/v2ce_hip_convupngrad.h, csrc/convupnwgrad.hip): the checked entry ``convupn_wgrad``.
+weight and input gradients through the upsample + concat at any of the decoders' channel counts that they stand on
+(include/v2ce_hip_convupngrad.h, csrc/convupnwgrad.hip: the checked entry ``convupn_wgrad``;
+include/v2ce_hip_convupndgrad.h, csrc/convupdgrad.hip: ``convupn_dgrad``).
 
     h1, s2, x1 = model.forward_dec2_sources(x)    # the frozen trunk up to dec2's two sources and dec3's skip tensor
     dec2 = Dec2Block.from_model(model)            # Dec2Convs -> Dec2Norms -> Dec2Conv: ten parameter tensors
@@ -13,13 +14,23 @@ weight gradients through the upsample + concat at any of the decoders' channel c
 
 With ``Dec2Conv`` (dec2_conv.py) this is the reference's whole ``ResidualBlock3D(192, 64, norm='BN', sn=True)``
 (train/scripts/model/submodules.py:249-264) at half the output resolution.  The channel counts of ``convupn_wgrad`` are read
-from the tensors; 64 + 32 -> 32 restates ``last_block.convup_wgrad`` byte for byte.  The gradient with respect to the two
-sources (a ``v2ce_convup_dgrad`` at 192 -> 64) has no consumer until ``UNet.decoders[1].conv2`` trains and is not provided:
-``Dec2Convs`` refuses sources that require grad.  There is no CPU path.
+from the tensors; 64 + 32 -> 32 restates ``last_block.convup_wgrad`` byte for byte, and ``convupn_dgrad`` at 64 + 32 -> 32
+``last_block.convup_dgrad``.
+
+The gradient with respect to the two sources is ``convupn_dgrad`` at 128 + 64 -> 64, and the layers that return it are
+classes of their own: ``Dec2ConvsThrough`` (built with ``input_grads=True``) and ``Dec2BlockThrough``,
+
+    dec2 = Dec2BlockThrough.from_model(model)     # the same ten parameters and state_dict keys as Dec2Block
+    h1 = mine(h1)                                 # a layer of the caller's own in front of a source
+    ... .backward()                               # h1.grad [B, L, 8, H / 4, ..] and s2.grad [B, L, 4, H / 2, ..] as well
+
+while ``Dec2Convs`` and ``Dec2Block`` keep refusing sources that require grad, as they always have: the package itself has
+no trainable layer in front of ``h1`` / ``s2`` yet (``UNet.decoders[1].conv2`` would be the first), so ``fit_dec2_block``
+trains what it trained.  There is no CPU path.
 """
 from __future__ import annotations
 
-from .conv_grads import TAPS, UPWGRAD_WANT as WANT, convupn_wgrad  # noqa: F401
+from .conv_grads import TAPS, UPDGRAD_WANT as DGRAD_WANT, UPWGRAD_WANT as WANT, convupn_dgrad, convupn_wgrad  # noqa: F401
 from .dec2_conv import Dec2Conv
 from .decoder_block import Conv1Layer, DecoderBlock, NormsLayer
 
@@ -49,15 +60,30 @@ class Dec2Convs(Conv1Layer):
     ``W_bar`` once and carries 1 / sigma in the epilogue scale, so in ``f16x2`` the forward is within the split-half
     bound of the model's, not byte-equal.
 
-    ``x0`` and ``x1`` get no gradient: a forward on inputs that require one raises.  ``guard`` (``f16x2``) holds the largest
-    range-guard bound of the layer's launches."""
+    ``x0`` and ``x1`` get no gradient from this class: a forward on inputs that require one raises, and so does
+    ``input_grads=True``.  ``Dec2ConvsThrough`` is the same layer with that gradient.  ``guard`` (``f16x2``) holds the
+    largest range-guard bound of the layer's launches."""
     C, C0, C1, INDEX = C, C0, C1, 2
     POWER_ITER, SHORTCUT, DGRAD, CHECK_WEIGHT_BAR = "kernel", "own", False, True
     NO_INPUT_GRADS = ("Dec2Convs provides no gradient with respect to x0 and x1 (the input gradient of conv1 and of the "
-                      "shortcut through the upsample, a convup_dgrad at 192 -> 64, is not implemented): pass tensors "
-                      "that do not require grad")
+                      "shortcut through the upsample, convupn_dgrad at 128 + 64 -> 64, is Dec2ConvsThrough's, built with "
+                      "input_grads=True, and Dec2BlockThrough's): pass tensors that do not require grad")
     # the entry, looked up in this module when it is called
     _wgrad = staticmethod(lambda *a, **k: convupn_wgrad(*a, **k))
+
+
+class Dec2ConvsThrough(Dec2Convs):
+    """``Dec2Convs`` with the gradient with respect to its two sources.  Built with ``input_grads=True`` (``from_model(model,
+    input_grads=True)``), a forward takes sources that require grad and the backward returns, next to the parameters'
+    gradients, ``d_x0`` (128 channels at the source resolution, a quarter of the network's) and ``d_x1`` (64 channels at
+    half): one ``convupn_dgrad`` call on the two weights with the normalisations folded in, only for the sources that
+    need it.  Built with ``input_grads=False`` it is ``Dec2Convs``.  The parameters, the buffers and the forward's bytes are
+    ``Dec2Convs``': either loads the other's ``state_dict``."""
+    DGRAD = True
+    NO_INPUT_GRADS = ("this Dec2ConvsThrough was built with input_grads=False and provides no gradient with respect to x0 and "
+                      "x1: build it with input_grads=True, or pass tensors that do not require grad")
+    # the entry, looked up in this module when it is called
+    _dgrad = staticmethod(lambda *a, **k: convupn_dgrad(*a, **k))
 
 
 class Dec2Norms(NormsLayer):
@@ -83,5 +109,18 @@ class Dec2Block(DecoderBlock):
         ... .backward()                               # dec2.convs / .norms / .conv parameters
         dec2.write_back(model)
 
-    The two sources get no gradient (``Dec2Convs``)."""
+    The two sources get no gradient (``Dec2Convs``); ``Dec2BlockThrough`` is the block that gives them one."""
     CONVS, NORMS, CONV = Dec2Convs, Dec2Norms, Dec2Conv
+
+
+class Dec2BlockThrough(DecoderBlock):
+    """``Dec2Block`` differentiable in both sources as well: ``Dec2ConvsThrough`` (input gradients on) ``-> Dec2Norms ->
+    Dec2Conv``.  A layer of the caller's own in front of ``h1`` or ``s2`` trains through it:
+
+        dec2 = Dec2BlockThrough.from_model(model)
+        x0_last = dec2(mine(h1), s2)                  # sources that require grad are taken
+        ... .backward()                               # mine's parameters, through d_x0 = convupn_dgrad(...)['x0']
+
+    The ten parameters and the ``state_dict`` keys are ``Dec2Block``'s, and on sources that do not require grad so is every
+    byte of the forward and of the parameters' gradients."""
+    CONVS, NORMS, CONV = Dec2ConvsThrough, Dec2Norms, Dec2Conv

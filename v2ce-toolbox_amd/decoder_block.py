@@ -20,9 +20,9 @@ is unified here.
                  ``V2ce3d._fold_bn``.  They differ in the last bit.
     SHORTCUT     (Conv1Layer, split-half) 'fused': one launch with the shortcut riding on conv1's; the guard is read from
                  z1's range slot.  'own': conv1's and the shortcut's own launch; the guard is read from the whole table.
-    DGRAD        (Conv1Layer) does ``convup_dgrad`` exist at these channel counts?  Where it does, a layer built with
-                 ``input_grads=True`` returns d_x0 / d_x1 and the forward saves the two weights for it; where it does not,
-                 sources that require grad are always refused.
+    DGRAD        (Conv1Layer) does the class have an input-gradient entry ``_dgrad`` (``convup_dgrad`` / ``convupn_dgrad``)?
+                 Where it does, a layer built with ``input_grads=True`` returns d_x0 / d_x1 and the forward saves the two
+                 weights for it; where it does not, sources that require grad are always refused.
     CHECK_WEIGHT_BAR  refuse a ``weight_bar`` that is not contiguous f32 (it is handed to a kernel as it is).
 
 There is no CPU path.
@@ -171,6 +171,9 @@ class _Conv2Fn(torch.autograd.Function):
                     y = model._conv(_planar_pitched(t), None, packed, sc, sh, C, 3, 1, hip.ACT_RELU,
                                     residual=_planar_pitched(res), split=False)
                     feat = model.to_c16(y)
+                    lw = getattr(t, "lw", t.shape[4])
+                    if feat.shape[4] > lw:               # (the exact-f32 launch never writes its padding columns, and
+                        feat[:, :, :, :, lw:, :] = 0     # torch.empty hands out whatever an earlier tensor left there)
                     layer._slot_out = None
         ctx.save_for_backward(t, feat, Wd, sc)
         ctx.lw, ctx.layer = getattr(t, "lw", t.shape[4]), layer

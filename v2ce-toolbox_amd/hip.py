@@ -80,6 +80,11 @@ CONVN_CHANNELS = (32, 64)                # what cin and cout may be
 CONVUPNGRAD_EXPORTS = ("v2ce_convupn_wgrad_workspace_bytes", "v2ce_convupn_wgrad")
 CONVUPN_C0, CONVUPN_C1, CONVUPN_COUT = (64, 128), (32, 64), (32, 64)     # what c0, c1 and cout may be
 
+# the input gradients of the same two layers with the channel counts as arguments, back through the concat and the upsample
+# (include/v2ce_hip_convupndgrad.h); c0, c1 and cout are those of CONVUPN_C0, CONVUPN_C1 and CONVUPN_COUT
+CONVUPNDGRAD_EXPORTS = ("v2ce_convupn_dgrad_workspace_bytes", "v2ce_convupn_dgrad")
+UPNDGRAD_TERMS = lambda cout: 28 * cout  # V2CE_UPNDGRAD_TERMS(cout): f32 terms of one d_X element (cout output channels x 28 units)
+
 
 LAYOUT_PLANAR, LAYOUT_C16 = 0, 1
 
@@ -357,6 +362,10 @@ def lib() -> ctypes.CDLL:
     L.v2ce_convupn_wgrad_workspace_bytes.restype = sz
     L.v2ce_convupn_wgrad.argtypes = [vp, vp, vp, vp] + [i32] * 9 + [vp, vp, vp, vp, sz, i32, vp]
     L.v2ce_convupn_wgrad.restype = ctypes.c_int
+    L.v2ce_convupn_dgrad_workspace_bytes.argtypes = [i32] * 10
+    L.v2ce_convupn_dgrad_workspace_bytes.restype = sz
+    L.v2ce_convupn_dgrad.argtypes = [vp, vp, vp, vp] + [i32] * 9 + [vp, vp, vp, sz, i32, vp]
+    L.v2ce_convupn_dgrad.restype = ctypes.c_int
     L.v2ce_voxelize_batch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
     L.v2ce_voxelize_batch_workspace_bytes.restype = sz
     L.v2ce_voxelize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
