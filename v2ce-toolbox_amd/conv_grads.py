@@ -1,8 +1,10 @@
 """The checked Python entries of the convolution gradient kernels the trainable decoder layers stand on
 (include/v2ce_hip_convgrad.h, v2ce_hip_convdgrad.h, v2ce_hip_convupgrad.h, v2ce_hip_convupdgrad.h, v2ce_hip_convngrad.h,
-v2ce_hip_convupngrad.h, v2ce_hip_convupndgrad.h; csrc/convnwgrad.hip, convndgrad.hip, convupnwgrad.hip, convupdgrad.hip):
+v2ce_hip_convcgrad.h, v2ce_hip_convupngrad.h, v2ce_hip_convupndgrad.h; csrc/convnwgrad.hip, convndgrad.hip, convupnwgrad.hip, convupdgrad.hip):
 
     convn_wgrad / convn_dgrad    a stride-1 3x3x3 convolution cin -> cout seen through the relu behind it
+    convc_wgrad / convc_dgrad    the same two with cin and cout each any of 32, 64, 128, 256, 512 (v2ce_convc_wgrad,
+                                 v2ce_convc_dgrad); convn_* stop at 64
     convupn_wgrad                the 3x3x3 and the 1x1x1 convolution c0 + c1 -> cout on cat(nearest_upsample_2x(x0), x1)
     convupn_dgrad                the input gradients of that pair, back through the concat and the upsample
     conv32_wgrad / conv32_dgrad / convup_wgrad / convup_dgrad
@@ -44,6 +46,8 @@ _CONVN_WGRAD = _Entry("v2ce_convn_wgrad", (hip.CONVN_CHANNELS, hip.CONVN_CHANNEL
 _CONV32_WGRAD = _Entry("v2ce_conv32_wgrad", ((32,), (32,)), False)
 _CONVN_DGRAD = _Entry("v2ce_convn_dgrad", (hip.CONVN_CHANNELS, hip.CONVN_CHANNELS), True)
 _CONV32_DGRAD = _Entry("v2ce_conv32_dgrad", ((32,), (32,)), False)
+_CONVC_WGRAD = _Entry("v2ce_convc_wgrad", (hip.CONVC_CHANNELS, hip.CONVC_CHANNELS), True)
+_CONVC_DGRAD = _Entry("v2ce_convc_dgrad", (hip.CONVC_CHANNELS, hip.CONVC_CHANNELS), True)
 _CONVUPN_WGRAD = _Entry("v2ce_convupn_wgrad", (hip.CONVUPN_C0, hip.CONVUPN_C1, hip.CONVUPN_COUT), True)
 _CONVUP_WGRAD = _Entry("v2ce_convup_wgrad", ((UP_C0,), (UP_C1,), (UP_COUT,)), False)
 _CONVUP_DGRAD = _Entry("v2ce_convup_dgrad", ((UP_C0,), (UP_C1,), (UP_COUT,)), False)
@@ -217,6 +221,35 @@ def conv32_dgrad(weight: torch.Tensor, y: Optional[torch.Tensor], upstream: torc
     """``convn_dgrad`` at 32 -> 32 through ``v2ce_conv32_dgrad``: ``weight`` is ``[32, 32, 3, 3, 3]``, every other tensor
     ``[B, L, 2, H, pitch, 16]``; anything else is refused."""
     return _dgrad(_CONV32_DGRAD, weight, y, upstream, want, out, max_workgroups)
+
+
+def convc_wgrad(x: torch.Tensor, y: Optional[torch.Tensor], upstream: torch.Tensor, *,
+                want: Sequence[str] = WGRAD_WANT, out: Optional[dict] = None, max_workgroups: int = 0) -> dict:
+    """``convn_wgrad`` with cin and cout each one of ``hip.CONVC_CHANNELS`` (32, 64, 128, 256, 512), through
+    ``v2ce_convc_wgrad``: the weight gradient of a stride-1, zero-padded 3x3x3 convolution cin -> cout seen through the relu
+    behind it.  ``x`` (the convolution's input, cin channels), ``y`` (the relu's output, or None: no mask) and ``upstream``
+    (the gradient with respect to ``y``; both cout channels) are channels-last-16 f32 with the same B, L, H, pitch and
+    ``.lw``.  -> {name: tensor} for the names in ``want`` (a subset of 'weight', 'shift'): 'weight' [cout, cin, 3, 3, 3] =
+    sum over the positions of m[co] x[ci] shifted by the tap, 'shift' [cout] = sum of m[co], with m = upstream where y > 0
+    else 0.  ``out``: {name: tensor} to write into.  ``max_workgroups``: 0 = the kernel's choice, n > 0 caps the shares of
+    the tile walk at max(n / pairs, 1), pairs = (cout / 32) (cin / 32) <= 256 (the result then depends on n only through
+    the order of the f64 sums).  At cin, cout in (32, 64) the bytes are ``convn_wgrad``'s.  One call, no host
+    synchronisation."""
+    return _wgrad(_CONVC_WGRAD, x, y, upstream, want, out, max_workgroups)
+
+
+def convc_dgrad(weight: torch.Tensor, y: Optional[torch.Tensor], upstream: torch.Tensor, *,
+                want: Sequence[str] = DGRAD_WANT, out: Optional[dict] = None, max_workgroups: int = 0) -> dict:
+    """``convn_dgrad`` with cin and cout each one of ``hip.CONVC_CHANNELS`` (32, 64, 128, 256, 512), through
+    ``v2ce_convc_dgrad``: the input gradient of a stride-1, zero-padded 3x3x3 convolution cin -> cout seen through the relu
+    behind it.  ``weight`` is the convolution's own contiguous ``[cout, cin, 3, 3, 3]`` f32 weight; ``y`` (the relu's
+    output, or None: no mask) and ``upstream`` (the gradient with respect to ``y``) are channels-last-16 f32 with cout
+    channels, the same shape and ``.lw``.  -> {name: tensor} for the names in ``want`` (a subset of 'x', 'res'): 'x' (cin
+    channels) = the transposed convolution of m with the weight, 'res' (cout channels) = m, with m = upstream where y > 0
+    else 0; both carry upstream's pitch and ``.lw`` and zeros in the padding columns ``lw .. pitch - 1``.  ``out``: {name:
+    tensor} to write into.  ``max_workgroups``: 0 = the kernel's choice, n > 0 caps the grid (the bytes do not depend on
+    n).  At cin, cout in (32, 64) the bytes are ``convn_dgrad``'s.  One call, no host synchronisation."""
+    return _dgrad(_CONVC_DGRAD, weight, y, upstream, want, out, max_workgroups)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

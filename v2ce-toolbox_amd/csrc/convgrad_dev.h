@@ -124,6 +124,13 @@ inline int plan_shares(long long tiles, int per, int max_workgroups) {
     return (int)shares;
 }
 
+// the channel counts of either side of a plain 3x3x3 convolution (convnwgrad.hip, convndgrad.hip): the widths of the UNet,
+// up to what the entry takes (64 for v2ce_convn_* and v2ce_conv32_*, kWidest for v2ce_convc_*)
+constexpr int kWidest = 512;
+inline bool channels_ok(int c, int widest) {
+    return (c == 32 || c == 64 || c == 128 || c == 256 || c == 512) && c <= widest;
+}
+
 inline size_t round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 // the workspace of `entry`: 8-byte aligned and at least `need` bytes -> V2CE_OK or the error, with the message set

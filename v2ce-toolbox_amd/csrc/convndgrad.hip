@@ -1,17 +1,22 @@
-// convndgrad.hip -- the input gradient of a 3x3x3 Conv3d(cin, cout) with 32 or 64 channels on either side on gfx950, seen
-// through the relu behind it (include/v2ce_hip_convngrad.h and, for the 32 -> 32 entry v2ce_conv32_dgrad,
-// include/v2ce_hip_convdgrad.h state the formulas, the tensors and the precision contract).  UNet.decoders[3].conv2 is the
-// 32 -> 32 case, UNet.decoders[2].conv2 the 64 -> 64 case.
+// convndgrad.hip -- the input gradient of a 3x3x3 Conv3d(cin, cout) with 32, 64, 128, 256 or 512 channels on either side on
+// gfx950, seen through the relu behind it (include/v2ce_hip_convcgrad.h; include/v2ce_hip_convngrad.h for the entry that
+// stops at 64 channels, v2ce_convn_dgrad, and include/v2ce_hip_convdgrad.h for the 32 -> 32 entry v2ce_conv32_dgrad state
+// the formulas, the tensors and the precision contract).  UNet.decoders[3].conv2 is the 32 -> 32 case, UNet.decoders[2].conv2
+// the 64 -> 64 case, UNet.decoders[1].conv2 the 128 -> 128 case.
 //
 // d_x is a GEMM with the positions as M, the input channels as N and (co group, tap, co) as K = 27 cout: per tap (kt, kh,
 // kw) a block D[pos][ci] += sum_co m[co][pos - tap + 1] W[co][ci][tap].  v_mfma_f32_32x32x2_f32 takes two output channels
 // per instruction: lane l holds A[pos = l & 31][k = l >> 5] and B[k = l >> 5][ci = l & 31].  A workgroup stages 32 channels
 // at a time, whatever cin and cout are, so the tile, the halo and the bank arguments do not depend on them:
 //   B  the weights, [tap][co][ci] after the prep kernel.  A wave keeps those of its taps (wave v takes the taps 7 v .. 7 v
-//      + 6, the last wave six) for its 32 input channels and EVERY co group in registers for the whole kernel: 7 taps x 16
-//      k-steps = 112 registers per lane and co group, 224 at cout = 64.  With the 64 accumulator registers that is under
-//      the 512 a wave may hold at four waves per workgroup (one workgroup per CU: the LDS decides the occupancy anyway),
-//      and nothing is fetched again inside the tile walk
+//      + 6, the last wave six) for its 32 input channels in registers: 7 taps x 16 k-steps = 112 registers per lane and co
+//      group.  Up to cout = 64 those of EVERY co group stay there for the whole kernel (224 registers at cout = 64; with
+//      the 64 accumulator registers that is under the 512 a wave may hold at four waves per workgroup -- one workgroup
+//      per CU: the LDS decides the occupancy anyway), and nothing is fetched again inside the tile walk.  Four co groups
+//      would need 448 + 64 registers, so from cout = 128 on a wave holds ONE co group at a time (the 112 registers of the
+//      cout = 32 instance) and fetches each group's weights again per tile, through L2: 28 KB per wave and group, issued
+//      in front of the group's halo staging and used behind its barrier, against the 448 MFMAs (28 600 cycles) the wave
+//      runs on them.  (Two groups at a time, the 224 registers of the cout = 64 instance plus the chunk walk, spill)
 //   A  the halo of m of ONE co group in LDS, channel-major: sH[co][halo position], 3 frames x 4 rows x 66 columns = 792
 //      positions at a plane stride of kPlane = 800 floats (= 32 mod 64).  The 32 lanes of a half read 32 consecutive
 //      columns of one row of one channel plane (consecutive banks); the other half reads the next plane, 32 banks further:
@@ -20,7 +25,7 @@
 // The grid is (cin / 32) x shares: workgroup s * gi + cig walks share s of the tiles for the input channels 32 cig .. + 31,
 // so one workgroup produces a whole d_x element.  A tile is 2 rows x 64 columns of one frame: four M groups of 32
 // positions, one accumulator (16 registers) each per wave.  Per tile the workgroup
-//   1. for co group 0, then co group 1 (cout = 64): stages m = y > 0 ? upstream : 0 of the group's halo into sH (zeros
+//   1. for co group 0, 1, ..., cout / 32 - 1 in that order: stages m = y > 0 ? upstream : 0 of the group's halo into sH (zeros
 //      outside the frame, the sequence and the row's W columns), writes d_res from the tile's own positions on the way
 //      (cig = 0 only) and runs its taps into the SAME accumulators: 4 independent MFMA chains per wave, 7 x 16 steps each
 //      per group;
@@ -33,6 +38,7 @@
 #include "convgrad_dev.h"
 
 #include "../../include/v2ce_hip_convdgrad.h"
+#include "../../include/v2ce_hip_convcgrad.h"
 #include "../../include/v2ce_hip_convngrad.h"
 
 namespace v2ce {
@@ -62,8 +68,27 @@ __global__ __launch_bounds__(kThreads) void ndgrad_prep_kernel(const float *__re
     wt[e] = weight[(size_t)rest * kTaps + tap];
 }
 
-// kCog: co groups of 32 output channels (cout / 32)
+// wave wv's B operands of the co groups cg0 .. cg0 + kCog - 1: step s of tap j and group cg is W[co = 32 (cg0 + cg) + 2 s +
+// (lane >> 5)][ci = 32 cig + (lane & 31)][tap]; zeros for a tap past the last one
 template <int kCog>
+__device__ __forceinline__ void load_weights(const float *__restrict__ wt, const Dims &D, int wv, int lane, int cig, int cg0,
+                                             bool doX, float (&wreg)[kCog][kTapsPerWave][kSteps]) {
+#pragma unroll
+    for (int j = 0; j < kTapsPerWave; ++j) {
+        const int tap = wv * kTapsPerWave + j;
+        const bool live = doX && tap < kTaps;
+#pragma unroll
+        for (int cg = 0; cg < kCog; ++cg)
+#pragma unroll
+            for (int s = 0; s < kSteps; ++s)
+                wreg[cg][j][s] =
+                    live ? wt[((size_t)tap * D.cout + (cg0 + cg) * kC + 2 * s + (lane >> 5)) * D.cin + cig * kC + (lane & 31)] : 0.0f;
+    }
+}
+
+// kCog: co groups of 32 output channels whose weights a wave holds at a time.  !kReload: cout = 32 kCog, they are loaded
+// once; kReload: cout is a multiple of 32 kCog and every chunk of kCog groups is loaded again per tile
+template <int kCog, bool kReload>
 __global__ __launch_bounds__(kThreads) void ndgrad_kernel(const float *__restrict__ wt, const float *__restrict__ y,
                                                           const float *__restrict__ up, Dims D, float *__restrict__ d_x,
                                                           float *__restrict__ d_res_arg) {
@@ -80,22 +105,17 @@ __global__ __launch_bounds__(kThreads) void ndgrad_kernel(const float *__restric
     if (!doX && !d_res) return;                      // (uniform)
     const int xplanes = D.cin / 16, mplanes = D.cout / 16;
 
-    // B operands of this wave's taps: step s of tap j and co group cg is W[co = 32 cg + 2 s + (lane >> 5)][ci = 32 cig +
-    // (lane & 31)][tap]
-    float wreg[kCog][kTapsPerWave][kSteps];
+    const int chunks = kReload ? D.cout / (kC * kCog) : 1;
+
+    float wreg[kCog][kTapsPerWave][kSteps];         // B operands of this wave's taps
     int tapoff[kTapsPerWave];                       // the tap's shift inside a plane of sH: m at pos - tap + 1
 #pragma unroll
     for (int j = 0; j < kTapsPerWave; ++j) {
         const int tap = wv * kTapsPerWave + j, kt = tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
         const bool live = doX && tap < kTaps;
         tapoff[j] = live ? ((2 - kt) * kHaloH + (2 - kh)) * kHaloW + (2 - kw) : 0;
-#pragma unroll
-        for (int cg = 0; cg < kCog; ++cg)
-#pragma unroll
-            for (int s = 0; s < kSteps; ++s)
-                wreg[cg][j][s] = live ? wt[((size_t)tap * D.cout + cg * kC + 2 * s + (lane >> 5)) * D.cin + cig * kC + (lane & 31)]
-                                      : 0.0f;
     }
+    if (!kReload) load_weights<kCog>(wt, D, wv, lane, cig, 0, doX, wreg);
 
     for (long long tile = t0; tile < t1; ++tile) {
         const TileAt ta = tile_at(D, tile);
@@ -108,62 +128,66 @@ __global__ __launch_bounds__(kThreads) void ndgrad_kernel(const float *__restric
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[gq][r] = 0.0f;
 
+        for (int chunk = 0; chunk < chunks; ++chunk) {
+            if (kReload) load_weights<kCog>(wt, D, wv, lane, cig, chunk * kCog, doX, wreg);
 #pragma unroll
-        for (int cg = 0; cg < kCog; ++cg) {
-            if (doX) __syncthreads();                // the previous tile's partials / the previous group's halo have been read
-            // the halo of m: 2 planes x 792 positions, 64 bytes each; consecutive lanes take consecutive positions
-            for (int i = t; i < 2 * kHalo; i += kThreads) {
-                const int g = i / kHalo, hp = i % kHalo;
-                const int dt = hp / (kHaloH * kHaloW), rem = hp % (kHaloH * kHaloW), hh = rem / kHaloW, ww = rem % kHaloW;
-                const int ll = l + dt - 1, h = h0 + hh - 1, w = w0 + ww - 1;
-                const bool own = dt == 1 && hh >= 1 && hh <= kTileH && ww >= 1 && ww <= kTileW;
-                if (!doX && !own) continue;
-                const bool inside = ll >= 0 && ll < D.L && h >= 0 && h < D.H && w >= 0 && w < D.W;
-                float4 v[4];
+            for (int cg = 0; cg < kCog; ++cg) {
+                const int cog = chunk * kCog + cg;       // the co group on its way
+                if (doX) __syncthreads();                // the previous tile's partials / group's halo have been read
+                // the halo of m: 2 planes x 792 positions, 64 bytes each; consecutive lanes take consecutive positions
+                for (int i = t; i < 2 * kHalo; i += kThreads) {
+                    const int g = i / kHalo, hp = i % kHalo;
+                    const int dt = hp / (kHaloH * kHaloW), rem = hp % (kHaloH * kHaloW), hh = rem / kHaloW, ww = rem % kHaloW;
+                    const int ll = l + dt - 1, h = h0 + hh - 1, w = w0 + ww - 1;
+                    const bool own = dt == 1 && hh >= 1 && hh <= kTileH && ww >= 1 && ww <= kTileW;
+                    if (!doX && !own) continue;
+                    const bool inside = ll >= 0 && ll < D.L && h >= 0 && h < D.H && w >= 0 && w < D.W;
+                    float4 v[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (inside) {
-                    const long long at = c16_at(D, mplanes, f + dt - 1, cg * 2 + g, h, w);
+                    for (int q = 0; q < 4; ++q) v[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    if (inside) {
+                        const long long at = c16_at(D, mplanes, f + dt - 1, cog * 2 + g, h, w);
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float4 *>(up + at + q * 4);
-                    if (y) {
+                        for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float4 *>(up + at + q * 4);
+                        if (y) {
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) v[q] = relu_mask(v[q], *reinterpret_cast<const float4 *>(y + at + q * 4));
+                            for (int q = 0; q < 4; ++q) v[q] = relu_mask(v[q], *reinterpret_cast<const float4 *>(y + at + q * 4));
+                        }
+                        if (own && d_res) {
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) *reinterpret_cast<float4 *>(d_res + at + q * 4) = v[q];
+                        }
                     }
-                    if (own && d_res) {
+                    if (doX) {
+                        float *dst = sH + (g * 16) * kPlane + hp;
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) *reinterpret_cast<float4 *>(d_res + at + q * 4) = v[q];
+                        for (int q = 0; q < 4; ++q) {
+                            dst[(q * 4 + 0) * kPlane] = v[q].x; dst[(q * 4 + 1) * kPlane] = v[q].y;
+                            dst[(q * 4 + 2) * kPlane] = v[q].z; dst[(q * 4 + 3) * kPlane] = v[q].w;
+                        }
                     }
                 }
-                if (doX) {
-                    float *dst = sH + (g * 16) * kPlane + hp;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        dst[(q * 4 + 0) * kPlane] = v[q].x; dst[(q * 4 + 1) * kPlane] = v[q].y;
-                        dst[(q * 4 + 2) * kPlane] = v[q].z; dst[(q * 4 + 3) * kPlane] = v[q].w;
-                    }
-                }
-            }
-            if (!doX) continue;                      // (uniform: d_res alone needs neither the LDS nor a barrier)
-            __syncthreads();
+                if (!doX) continue;                      // (uniform: d_res alone needs neither the LDS nor a barrier)
+                __syncthreads();
 
-            // group gq = (row gq >> 1, columns 32 (gq & 1) ..): lane's position inside a plane before the tap's shift
-            const float *a0 = sH + (lane >> 5) * kPlane + (lane & 31);
+                // group gq = (row gq >> 1, columns 32 (gq & 1) ..): lane's position inside a plane before the tap's shift
+                const float *a0 = sH + (lane >> 5) * kPlane + (lane & 31);
 #pragma unroll
-            for (int j = 0; j < kTapsPerWave; ++j) {
-                if (j < ntaps) {
-                    const float *aj = a0 + tapoff[j];
+                for (int j = 0; j < kTapsPerWave; ++j) {
+                    if (j < ntaps) {
+                        const float *aj = a0 + tapoff[j];
 #pragma unroll
-                    for (int s = 0; s < kSteps; ++s) {
+                        for (int s = 0; s < kSteps; ++s) {
 #pragma unroll
-                        for (int gq = 0; gq < kGroups; ++gq) {
-                            const float a = aj[2 * s * kPlane + (gq >> 1) * kHaloW + (gq & 1) * 32];
-                            acc[gq] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wreg[cg][j][s], acc[gq], 0, 0, 0);
+                            for (int gq = 0; gq < kGroups; ++gq) {
+                                const float a = aj[2 * s * kPlane + (gq >> 1) * kHaloW + (gq & 1) * 32];
+                                acc[gq] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wreg[cg][j][s], acc[gq], 0, 0, 0);
+                            }
                         }
                     }
                 }
             }
-        }
+            }
 
         if (tw == D.tiles_w - 1 && D.pitch > D.W) {
             // the padding columns of the tile's rows: (row, plane, column, piece of 16 bytes); the planes of d_x are this
@@ -219,8 +243,9 @@ __global__ __launch_bounds__(kThreads) void ndgrad_kernel(const float *__restric
     }
 }
 
-bool make_dims(int cin, int cout, int B, int L, int H, int W, int pitch, int max_workgroups, Dims &D) {
-    if ((cin != 32 && cin != 64) || (cout != 32 && cout != 64)) return false;
+// widest: the most channels the calling entry takes on either side (64: v2ce_convn_dgrad and v2ce_conv32_dgrad)
+bool make_dims(int widest, int cin, int cout, int B, int L, int H, int W, int pitch, int max_workgroups, Dims &D) {
+    if (!channels_ok(cin, widest) || !channels_ok(cout, widest)) return false;
     if (!make_extent(B, L, H, W, pitch, false, 0, max_workgroups, D)) return false;
     D.cin = cin; D.cout = cout; D.gi = cin / kC;
     D.shares = plan_shares(D.tiles, D.gi, max_workgroups);
@@ -228,18 +253,18 @@ bool make_dims(int cin, int cout, int B, int L, int H, int W, int pitch, int max
     return true;
 }
 
-const char *kNeeds = "needs cin, cout in {32, 64}, B, L, H, W >= 1, pitch >= W, max_workgroups >= 0, B L H W < 2^31 and "
-                     "B L H pitch < 2^34";
+const char *kNeeds = "B, L, H, W >= 1, pitch >= W, max_workgroups >= 0, B L H W < 2^31 and B L H pitch < 2^34";
+const char *needs_channels(int widest) { return widest > 64 ? "{32, 64, 128, 256, 512}" : "{32, 64}"; }
 
 // `entry`: the symbol the caller used; it leads every message
-int ndgrad(const char *entry, const float *weight, const float *y, const float *upstream, int cin, int cout, int B, int L, int H,
+int ndgrad(const char *entry, int widest, const float *weight, const float *y, const float *upstream, int cin, int cout, int B, int L, int H,
            int W, int pitch, float *d_x, float *d_res, void *workspace, size_t workspace_bytes, int max_workgroups,
            v2ce_stream_t stream) {
     clear_error();
     Dims D;
-    V2CE_REQUIRE(make_dims(cin, cout, B, L, H, W, pitch, max_workgroups, D), V2CE_ERR_BAD_ARG,
-                 "%s: cin %d cout %d B %d L %d H %d W %d pitch %d max_workgroups %d: %s", entry, cin, cout, B, L, H, W, pitch,
-                 max_workgroups, kNeeds);
+    V2CE_REQUIRE(make_dims(widest, cin, cout, B, L, H, W, pitch, max_workgroups, D), V2CE_ERR_BAD_ARG,
+                 "%s: cin %d cout %d B %d L %d H %d W %d pitch %d max_workgroups %d: needs cin, cout in %s, %s", entry, cin, cout, B,
+                 L, H, W, pitch, max_workgroups, needs_channels(widest), kNeeds);
     V2CE_REQUIRE(weight && upstream && workspace, V2CE_ERR_BAD_ARG, "%s: null pointer", entry);
     V2CE_REQUIRE(d_x || d_res, V2CE_ERR_BAD_ARG, "%s: no output requested (d_x and d_res are both null)", entry);
     V2CE_REQUIRE(aligned16(y, upstream, d_x, d_res), V2CE_ERR_BAD_ARG, "%s: y, upstream, d_x and d_res must be 16-byte aligned",
@@ -248,7 +273,8 @@ int ndgrad(const char *entry, const float *weight, const float *y, const float *
     if (const int rc = check_workspace(entry, workspace, workspace_bytes, D.total)) return rc;
     hipStream_t st = as_stream(stream);
     float *wt = static_cast<float *>(workspace);
-    const auto kernel = cout == 64 ? ndgrad_kernel<2> : ndgrad_kernel<1>;
+    // up to two co groups stay in registers; from 128 output channels on they come one at a time, again per tile
+    const auto kernel = cout > 64 ? ndgrad_kernel<1, true> : cout == 64 ? ndgrad_kernel<2, false> : ndgrad_kernel<1, false>;
     if (d_x) {
         const int weights = kTaps * cout * cin;
         V2CE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -269,17 +295,30 @@ using namespace v2ce;
 
 extern "C" size_t v2ce_convn_dgrad_workspace_bytes(int cin, int cout, int B, int L, int H, int W, int pitch, int max_workgroups) {
     Dims D;
-    return make_dims(cin, cout, B, L, H, W, pitch, max_workgroups, D) ? D.total : 0;
+    return make_dims(64, cin, cout, B, L, H, W, pitch, max_workgroups, D) ? D.total : 0;
 }
 
 extern "C" int v2ce_convn_dgrad(const float *weight, const float *y, const float *upstream, int cin, int cout, int B, int L, int H,
                                 int W, int pitch, float *d_x, float *d_res, void *workspace, size_t workspace_bytes,
                                 int max_workgroups, v2ce_stream_t stream) {
-    return ndgrad("v2ce_convn_dgrad", weight, y, upstream, cin, cout, B, L, H, W, pitch, d_x, d_res, workspace, workspace_bytes,
+    return ndgrad("v2ce_convn_dgrad", 64, weight, y, upstream, cin, cout, B, L, H, W, pitch, d_x, d_res, workspace, workspace_bytes,
                   max_workgroups, stream);
 }
 
-// the 32 -> 32 entries of include/v2ce_hip_convdgrad.h: ndgrad_kernel<1> with one ci group
+// the entries of include/v2ce_hip_convcgrad.h: every width of the UNet on either side
+extern "C" size_t v2ce_convc_dgrad_workspace_bytes(int cin, int cout, int B, int L, int H, int W, int pitch, int max_workgroups) {
+    Dims D;
+    return make_dims(kWidest, cin, cout, B, L, H, W, pitch, max_workgroups, D) ? D.total : 0;
+}
+
+extern "C" int v2ce_convc_dgrad(const float *weight, const float *y, const float *upstream, int cin, int cout, int B, int L, int H,
+                                int W, int pitch, float *d_x, float *d_res, void *workspace, size_t workspace_bytes,
+                                int max_workgroups, v2ce_stream_t stream) {
+    return ndgrad("v2ce_convc_dgrad", kWidest, weight, y, upstream, cin, cout, B, L, H, W, pitch, d_x, d_res, workspace,
+                  workspace_bytes, max_workgroups, stream);
+}
+
+// the 32 -> 32 entries of include/v2ce_hip_convdgrad.h: ndgrad_kernel<1, false> with one ci group
 extern "C" size_t v2ce_conv32_dgrad_workspace_bytes(int B, int L, int H, int W, int pitch, int max_workgroups) {
     return v2ce_convn_dgrad_workspace_bytes(32, 32, B, L, H, W, pitch, max_workgroups);
 }
@@ -287,6 +326,6 @@ extern "C" size_t v2ce_conv32_dgrad_workspace_bytes(int B, int L, int H, int W, 
 extern "C" int v2ce_conv32_dgrad(const float *weight, const float *y, const float *upstream, int B, int L, int H, int W, int pitch,
                                  float *d_x, float *d_res, void *workspace, size_t workspace_bytes, int max_workgroups,
                                  v2ce_stream_t stream) {
-    return ndgrad("v2ce_conv32_dgrad", weight, y, upstream, 32, 32, B, L, H, W, pitch, d_x, d_res, workspace, workspace_bytes,
+    return ndgrad("v2ce_conv32_dgrad", 64, weight, y, upstream, 32, 32, B, L, H, W, pitch, d_x, d_res, workspace, workspace_bytes,
                   max_workgroups, stream);
 }

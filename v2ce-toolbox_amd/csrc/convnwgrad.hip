@@ -1,7 +1,8 @@
-// convnwgrad.hip -- the weight gradient of a 3x3x3 Conv3d(cin, cout) with 32 or 64 channels on either side on gfx950, seen
-// through the relu behind it (include/v2ce_hip_convngrad.h and, for the 32 -> 32 entry v2ce_conv32_wgrad,
-// include/v2ce_hip_convgrad.h state the formulas, the tensors and the precision contract).  UNet.decoders[3].conv2 is the
-// 32 -> 32 case, UNet.decoders[2].conv2 the 64 -> 64 case.
+// convnwgrad.hip -- the weight gradient of a 3x3x3 Conv3d(cin, cout) with 32, 64, 128, 256 or 512 channels on either side on
+// gfx950, seen through the relu behind it (include/v2ce_hip_convcgrad.h; include/v2ce_hip_convngrad.h for the entry that
+// stops at 64 channels, v2ce_convn_wgrad, and include/v2ce_hip_convgrad.h for the 32 -> 32 entry v2ce_conv32_wgrad state
+// the formulas, the tensors and the precision contract).  UNet.decoders[3].conv2 is the 32 -> 32 case, UNet.decoders[2].conv2
+// the 64 -> 64 case, UNet.decoders[1].conv2 the 128 -> 128 case.
 //
 // d_weight is (cout / 32) x (cin / 32) blocks of a 32 x 864 GEMM whose K runs over every output position, one block per pair
 // of channel groups.  Per tap (kt, kh, kw) a 32 x 32 block D[co][ci] += sum_pos m[co][pos] x[ci][pos + tap].
@@ -28,6 +29,7 @@
 // the shares 0 .. shares - 1 and rounds once.
 #include "convgrad_dev.h"
 
+#include "../../include/v2ce_hip_convcgrad.h"
 #include "../../include/v2ce_hip_convngrad.h"
 
 namespace v2ce {
@@ -163,8 +165,10 @@ __global__ __launch_bounds__(kThreads) void nwgrad_finish_kernel(const double *_
     }
 }
 
-bool make_dims(int cin, int cout, int B, int L, int H, int W, int pitch, int max_workgroups, Dims &D) {
-    if ((cin != 32 && cin != 64) || (cout != 32 && cout != 64)) return false;
+// widest: the most channels the calling entry takes on either side (64: v2ce_convn_wgrad and v2ce_conv32_wgrad).  At 512
+// -> 512 there are 256 pairs and one share: 256 x kPartial f64 = 56 MB, the most the workspace ever is
+bool make_dims(int widest, int cin, int cout, int B, int L, int H, int W, int pitch, int max_workgroups, Dims &D) {
+    if (!channels_ok(cin, widest) || !channels_ok(cout, widest)) return false;
     if (!make_extent(B, L, H, W, pitch, false, 0, max_workgroups, D)) return false;
     D.cin = cin; D.cout = cout; D.gi = cin / kC; D.go = cout / kC; D.pairs = D.gi * D.go;
     D.shares = plan_shares(D.tiles, D.pairs, max_workgroups);
@@ -172,18 +176,18 @@ bool make_dims(int cin, int cout, int B, int L, int H, int W, int pitch, int max
     return true;
 }
 
-const char *kNeeds = "needs cin, cout in {32, 64}, B, L, H, W >= 1, pitch >= W, max_workgroups >= 0, B L H W < 2^31 and "
-                     "B L H pitch < 2^34";
+const char *kNeeds = "B, L, H, W >= 1, pitch >= W, max_workgroups >= 0, B L H W < 2^31 and B L H pitch < 2^34";
+const char *needs_channels(int widest) { return widest > 64 ? "{32, 64, 128, 256, 512}" : "{32, 64}"; }
 
 // `entry`: the symbol the caller used; it leads every message
-int nwgrad(const char *entry, const float *x, const float *y, const float *upstream, int cin, int cout, int B, int L, int H, int W,
+int nwgrad(const char *entry, int widest, const float *x, const float *y, const float *upstream, int cin, int cout, int B, int L, int H, int W,
            int pitch, float *d_weight, float *d_shift, void *workspace, size_t workspace_bytes, int max_workgroups,
            v2ce_stream_t stream) {
     clear_error();
     Dims D;
-    V2CE_REQUIRE(make_dims(cin, cout, B, L, H, W, pitch, max_workgroups, D), V2CE_ERR_BAD_ARG,
-                 "%s: cin %d cout %d B %d L %d H %d W %d pitch %d max_workgroups %d: %s", entry, cin, cout, B, L, H, W, pitch,
-                 max_workgroups, kNeeds);
+    V2CE_REQUIRE(make_dims(widest, cin, cout, B, L, H, W, pitch, max_workgroups, D), V2CE_ERR_BAD_ARG,
+                 "%s: cin %d cout %d B %d L %d H %d W %d pitch %d max_workgroups %d: needs cin, cout in %s, %s", entry, cin, cout, B,
+                 L, H, W, pitch, max_workgroups, needs_channels(widest), kNeeds);
     V2CE_REQUIRE(x && upstream && workspace, V2CE_ERR_BAD_ARG, "%s: null pointer", entry);
     V2CE_REQUIRE(d_weight || d_shift, V2CE_ERR_BAD_ARG, "%s: no output requested (d_weight and d_shift are both null)", entry);
     V2CE_REQUIRE(aligned16(x, y, upstream), V2CE_ERR_BAD_ARG, "%s: x, y and upstream must be 16-byte aligned", entry);
@@ -209,14 +213,27 @@ using namespace v2ce;
 
 extern "C" size_t v2ce_convn_wgrad_workspace_bytes(int cin, int cout, int B, int L, int H, int W, int pitch, int max_workgroups) {
     Dims D;
-    return make_dims(cin, cout, B, L, H, W, pitch, max_workgroups, D) ? D.total : 0;
+    return make_dims(64, cin, cout, B, L, H, W, pitch, max_workgroups, D) ? D.total : 0;
 }
 
 extern "C" int v2ce_convn_wgrad(const float *x, const float *y, const float *upstream, int cin, int cout, int B, int L, int H,
                                 int W, int pitch, float *d_weight, float *d_shift, void *workspace, size_t workspace_bytes,
                                 int max_workgroups, v2ce_stream_t stream) {
-    return nwgrad("v2ce_convn_wgrad", x, y, upstream, cin, cout, B, L, H, W, pitch, d_weight, d_shift, workspace, workspace_bytes,
+    return nwgrad("v2ce_convn_wgrad", 64, x, y, upstream, cin, cout, B, L, H, W, pitch, d_weight, d_shift, workspace, workspace_bytes,
                   max_workgroups, stream);
+}
+
+// the entries of include/v2ce_hip_convcgrad.h: every width of the UNet on either side, up to 16 x 16 pairs
+extern "C" size_t v2ce_convc_wgrad_workspace_bytes(int cin, int cout, int B, int L, int H, int W, int pitch, int max_workgroups) {
+    Dims D;
+    return make_dims(kWidest, cin, cout, B, L, H, W, pitch, max_workgroups, D) ? D.total : 0;
+}
+
+extern "C" int v2ce_convc_wgrad(const float *x, const float *y, const float *upstream, int cin, int cout, int B, int L, int H,
+                                int W, int pitch, float *d_weight, float *d_shift, void *workspace, size_t workspace_bytes,
+                                int max_workgroups, v2ce_stream_t stream) {
+    return nwgrad("v2ce_convc_wgrad", kWidest, x, y, upstream, cin, cout, B, L, H, W, pitch, d_weight, d_shift, workspace,
+                  workspace_bytes, max_workgroups, stream);
 }
 
 // the 32 -> 32 entries of include/v2ce_hip_convgrad.h: one pair
@@ -227,6 +244,6 @@ extern "C" size_t v2ce_conv32_wgrad_workspace_bytes(int B, int L, int H, int W, 
 extern "C" int v2ce_conv32_wgrad(const float *x, const float *y, const float *upstream, int B, int L, int H, int W, int pitch,
                                  float *d_weight, float *d_shift, void *workspace, size_t workspace_bytes, int max_workgroups,
                                  v2ce_stream_t stream) {
-    return nwgrad("v2ce_conv32_wgrad", x, y, upstream, 32, 32, B, L, H, W, pitch, d_weight, d_shift, workspace, workspace_bytes,
+    return nwgrad("v2ce_conv32_wgrad", 64, x, y, upstream, 32, 32, B, L, H, W, pitch, d_weight, d_shift, workspace, workspace_bytes,
                   max_workgroups, stream);
 }

@@ -24,9 +24,9 @@ classes of their own: ``Dec2ConvsThrough`` (built with ``input_grads=True``) and
     h1 = mine(h1)                                 # a layer of the caller's own in front of a source
     ... .backward()                               # h1.grad [B, L, 8, H / 4, ..] and s2.grad [B, L, 4, H / 2, ..] as well
 
-while ``Dec2Convs`` and ``Dec2Block`` keep refusing sources that require grad, as they always have: the package itself has
-no trainable layer in front of ``h1`` / ``s2`` yet (``UNet.decoders[1].conv2`` would be the first), so ``fit_dec2_block``
-trains what it trained.  There is no CPU path.
+while ``Dec2Convs`` and ``Dec2Block`` keep refusing sources that require grad, as they always have, so ``fit_dec2_block``
+trains what it trained.  The package's own layer in front of ``h1`` is ``dec1_conv.Dec1Conv`` (``UNet.decoders[1].conv2``),
+and ``finetune.fit_dec1_conv`` trains it through ``Dec2BlockThrough``.  There is no CPU path.
 """
 from __future__ import annotations
 

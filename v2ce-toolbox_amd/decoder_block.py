@@ -8,7 +8,8 @@
 
 Each role has one autograd ``Function``; a block of the network is a subclass that sets the channel counts, the block's
 index from the end of ``UNet.decoders``, the gradient entries it calls and the policies below.  last_conv.py / last_block.py
-hold the subclasses of ``UNet.decoders[-1]`` (32 channels), dec2_conv.py / dec2_block.py those of ``UNet.decoders[-2]`` (64).
+hold the subclasses of ``UNet.decoders[-1]`` (32 channels), dec2_conv.py / dec2_block.py those of ``UNet.decoders[-2]`` (64),
+dec1_conv.py the conv2 of ``UNet.decoders[-3]`` (128).
 
 The policies are differences between the two blocks that are real: each moves bytes, so each is a named switch and none
 is unified here.
@@ -209,8 +210,11 @@ class _Conv2Fn(torch.autograd.Function):
 class Conv2Layer(_SpectralConv):
     """``conv2`` + ``bn2`` + shortcut add + relu of ``UNet.decoders[-INDEX]`` as a trainable module, the layer in
     ``.eval()``: the BatchNorm statistics are frozen, its affine parameters and the convolution's ``weight_bar`` [C, C, 3, 3,
-    3] train.  A subclass sets ``C``, ``INDEX``, the policies and ``_wgrad`` / ``_dgrad``, the two gradient entries."""
+    3] train.  A subclass sets ``C``, ``INDEX``, the policies, ``_wgrad`` / ``_dgrad``, the two gradient entries, and, where
+    those take more than ``hip.CONVN_CHANNELS``, ``CHANNELS``: the channel counts a tensor may have at all (what the
+    refusal of a tensor in another layout names)."""
     BN_FOLD = "rsqrt"
+    CHANNELS = hip.CONVN_CHANNELS
 
     def __init__(self, model=None):
         super().__init__()
@@ -254,10 +258,10 @@ class Conv2Layer(_SpectralConv):
         ``f16x2`` its range slot ``.absmax`` (max |.| per batch element, what the model's launch leaves) and a
         ``grad_fn``."""
         model, C = self._launch_model(), self.C
-        dims = _check_c16(t, "t", hip.CONVN_CHANNELS)
+        dims = _check_c16(t, "t", self.CHANNELS)
         if dims[0] != C:
             raise ValueError(f"t must have {C} channels [b, l, {C // 16}, h0, pitch0, 16], got {tuple(t.shape)}")
-        if _check_c16(res, "res", hip.CONVN_CHANNELS) != dims or res.shape != t.shape or res.device != t.device:
+        if _check_c16(res, "res", self.CHANNELS) != dims or res.shape != t.shape or res.device != t.device:
             raise ValueError(f"res {tuple(res.shape)} must match t {tuple(t.shape)}")
         self._check_weight_bar()
         W, scale, shift = self.effective()

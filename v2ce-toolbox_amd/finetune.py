@@ -505,6 +505,100 @@ def fit_dec2_block(model, image_units, gt_voxels, *, train: Sequence[str] = DEC2
     return history
 
 
+DEC1_CONV_GROUPS = DEC2_BLOCK_GROUPS + ("dec1_conv2", "dec1_bn2")
+
+
+def fit_dec1_conv(model, image_units, gt_voxels, *, train: Sequence[str] = DEC1_CONV_GROUPS,
+                  loss: Sequence[str] = losses.DEFAULT_LOSS, steps: int, lr: float, optimizer: str = "adam",
+                  cache_bytes: int = DEFAULT_CACHE_BYTES, **loss_options) -> List[dict]:
+    """Fit the last two decoder blocks, ``UNet.pred`` and the layer in front of them: what ``fit_dec2_block`` trains, and
+    ``UNet.decoders[1].conv2`` -- the spectral-normalised 3x3x3 ``Conv3d(128, 128)`` at a quarter of the resolution whose
+    output ``UNet.decoders[2]`` upsamples -- with its ``bn2``, through the input gradient of ``UNet.decoders[2]``'s first
+    half (``v2ce_convupn_dgrad``) and the 128-channel gradients of ``v2ce_convc_wgrad`` / ``v2ce_convc_dgrad``.
+
+    ``train`` names the parameter groups one optimizer steps: those of ``fit_dec2_block``, 'dec1_conv2' (the convolution's
+    ``weight_bar``) and 'dec1_bn2' (weight and bias; the statistics stay frozen).  The other arguments and the returned
+    history are those of ``fit_dec2_block``.  With neither of the two in ``train`` this is ``fit_dec2_block`` with the same
+    arguments, step for step.
+
+    The convolution's two inputs and the skip tensors of the two blocks behind it (``V2ce3d.forward_dec1_inputs``) are
+    computed once per window and kept while the kept ones fit in ``cache_bytes``; every step is ``Dec1Conv`` ->
+    ``Dec2BlockThrough`` (asked for the gradient of ``h1`` alone) -> ``LastBlock`` -> ``PredHead`` ->
+    ``losses.calculate_loss`` -> ``backward()`` -> one optimizer step.  As in the reference, every forward of a trained
+    convolution advances its spectral-norm u / v by one power iteration.
+
+    On return the model differs from its state on entry in the trained tensors and in the ``weight_u`` / ``weight_v`` of
+    ``UNet.decoders[1].conv2`` and of the two convolutions of each of the two blocks behind it, which keep the iterations
+    the fit applied; the other seven spectral-norm layers and the call counter are restored."""
+    from .dec1_conv import Dec1Conv
+    from .dec2_block import Dec2BlockThrough
+    from .last_block import LastBlock
+    train = tuple(train)
+    if not train or any(g not in DEC1_CONV_GROUPS for g in train) or len(set(train)) != len(train):
+        raise ValueError(f"train must be a non-empty subset of {DEC1_CONV_GROUPS}, got {train}")
+    if not any(g in train for g in ("dec1_conv2", "dec1_bn2")):
+        return fit_dec2_block(model, image_units, gt_voxels, train=train, loss=loss, steps=steps, lr=lr, optimizer=optimizer,
+                              cache_bytes=cache_bytes, **loss_options)
+    loss = losses.check_loss_names(loss)
+    if optimizer not in ("adam", "sgd"):
+        raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
+    if int(steps) < 0:
+        raise ValueError(f"steps must be >= 0, got {steps}")
+    windows = _windows(image_units, gt_voxels)
+    head, block, dec2 = PredHead.from_model(model), LastBlock.from_model(model), Dec2BlockThrough.from_model(model)
+    dec1 = Dec1Conv.from_model(model)
+    convs, norms, conv = block.convs, block.norms, block.conv
+    groups = {"pred": [head.weight, head.bias], "conv2": [conv.weight_bar], "bn2": [conv.bn_weight, conv.bn_bias],
+              "bn1": [norms.bn1_weight, norms.bn1_bias], "bnd": [norms.bnd_weight, norms.bnd_bias],
+              "conv1": [convs.weight_bar],
+              "convd": [convs.short_weight] + ([convs.short_bias] if convs.short_bias is not None else []),
+              "dec2_conv2": [dec2.conv.weight_bar], "dec2_bn2": [dec2.conv.bn_weight, dec2.conv.bn_bias],
+              "dec2_conv1": [dec2.convs.weight_bar],
+              "dec2_convd": [dec2.convs.short_weight] + ([dec2.convs.short_bias] if dec2.convs.short_bias is not None else []),
+              "dec2_bn1": [dec2.norms.bn1_weight, dec2.norms.bn1_bias], "dec2_bnd": [dec2.norms.bnd_weight, dec2.norms.bnd_bias],
+              "dec1_conv2": [dec1.weight_bar], "dec1_bn2": [dec1.bn_weight, dec1.bn_bias]}
+    for g, ps in groups.items():
+        for p in ps:
+            p.requires_grad_(g in train)
+    opt = (torch.optim.Adam if optimizer == "adam" else torch.optim.SGD)([p for g in train for p in groups[g]], lr=lr)
+    snap = model.sn_snapshot()
+    cache, used = {}, 0
+
+    def inputs(i):
+        nonlocal used
+        if i in cache:
+            return cache[i]
+        model.sn_restore(snap)
+        four = model.forward_dec1_inputs(windows[i][0])
+        nb = sum(a.numel() for a in four) * 4
+        if used + nb <= cache_bytes:
+            cache[i], used = four, used + nb
+        return four
+
+    history = []
+    try:
+        for k in range(int(steps)):
+            i = k % len(windows)
+            opt.zero_grad(set_to_none=True)
+            t1, res1, s2, x1 = inputs(i)
+            pred = head(block(dec2(dec1(t1, res1), s2), x1))
+            total, d = losses.calculate_loss(pred, windows[i][1].contiguous(), loss=loss, **loss_options)
+            total.backward()
+            opt.step()
+            history.append({"loss": float(total.detach()), "loss_dict": {n: float(v) for n, v in d.items()}})
+    finally:
+        model.sn_restore(snap)
+    bound = max(float(conv.guard), float(convs.guard), float(dec2.conv.guard), float(dec2.convs.guard), float(dec1.guard))
+    if model.precision == "f16x2" and bound > model.RANGE_GUARD_LIMIT:
+        logger.warning(f"split-half range guard of the trained convolutions: bound {bound:.3e} > "
+                       f"{model.RANGE_GUARD_LIMIT:.1e}; fit with precision='f32'")
+    head.write_back(model)
+    block.write_back(model)
+    dec2.write_back(model)
+    dec1.write_back(model)
+    return history
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # command line
 
@@ -539,13 +633,14 @@ def build_parser():
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--optimizer", default="adam", choices=("adam", "sgd"))
-    p.add_argument("--train", default="head", choices=("head", "tail", "tail_norms", "last_block", "dec2_conv2", "dec2_block"),
+    p.add_argument("--train", default="head", choices=("head", "tail", "tail_norms", "last_block", "dec2_conv2", "dec2_block", "dec1_conv2"),
                    help="head: UNet.pred alone (fit_head); tail: the last decoder convolution, its bn2 and UNet.pred (fit_tail); "
                         "tail_norms: those and the last decoder block's bn1 and downsample.1 (fit_tail_norms); "
                         "last_block: those and the block's conv1 and shortcut convolution, the whole last decoder block "
                         "(fit_last_block); dec2_conv2: those and the second convolution of the decoder in front, UNet.decoders[2].conv2 "
                         "with its bn2 (fit_dec2_conv); dec2_block: those and that decoder's conv1, shortcut convolution, bn1 and downsample.1, "
-                        "the whole of UNet.decoders[2] (fit_dec2_block)")
+                        "the whole of UNet.decoders[2] (fit_dec2_block); dec1_conv2: those and the second convolution of the decoder in "
+                        "front of that, UNet.decoders[1].conv2 with its bn2 (fit_dec1_conv)")
     p.add_argument("--cache_gb", type=float, default=DEFAULT_CACHE_BYTES / 2 ** 30, help="feature cache budget")
     p.add_argument("-o", "--out", type=str, default="./tuned.pt", help="the tuned state_dict (v2ce.py -m loads it)")
     p.add_argument("--history", type=str, default=None, help="the per-step history as JSON (default: <out>.history.json)")
@@ -614,7 +709,7 @@ def main(argv=None):
     opts = {k: getattr(args, k) for k in ("ef_type", "add_base_loss", "alpha_pyramid", "alpha_ef", "alpha_efc",
                                           "alpha_match", "alpha_compensation", "alpha_pt", "alpha_norm")}
     fit = {"head": fit_head, "tail": fit_tail, "tail_norms": fit_tail_norms, "last_block": fit_last_block,
-           "dec2_conv2": fit_dec2_conv, "dec2_block": fit_dec2_block}[args.train]
+           "dec2_conv2": fit_dec2_conv, "dec2_block": fit_dec2_block, "dec1_conv2": fit_dec1_conv}[args.train]
     history = fit(model, xs, gs, loss=names, steps=args.steps, lr=args.lr, optimizer=args.optimizer,
                   cache_bytes=int(args.cache_gb * 2 ** 30), **opts)
     os.makedirs(op.dirname(op.abspath(args.out)), exist_ok=True)

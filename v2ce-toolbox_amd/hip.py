@@ -75,6 +75,12 @@ CONVNGRAD_EXPORTS = ("v2ce_convn_wgrad_workspace_bytes", "v2ce_convn_wgrad", "v2
                      "v2ce_convn_dgrad")
 CONVN_CHANNELS = (32, 64)                # what cin and cout may be
 
+# the same two gradients with any width of the UNet on either side: UNet.decoders[1].conv2 and every 3x3x3 convolution in
+# front of it (include/v2ce_hip_convcgrad.h)
+CONVCGRAD_EXPORTS = ("v2ce_convc_wgrad_workspace_bytes", "v2ce_convc_wgrad", "v2ce_convc_dgrad_workspace_bytes",
+                     "v2ce_convc_dgrad")
+CONVC_CHANNELS = (32, 64, 128, 256, 512)  # what cin and cout may be
+
 # the weight gradients of a decoder block's conv1 and shortcut on the upsample + concat input with the channel counts as
 # arguments: UNet.decoders[2].conv1 and .downsample[0] (include/v2ce_hip_convupngrad.h)
 CONVUPNGRAD_EXPORTS = ("v2ce_convupn_wgrad_workspace_bytes", "v2ce_convupn_wgrad")
@@ -358,6 +364,14 @@ def lib() -> ctypes.CDLL:
     L.v2ce_convn_dgrad_workspace_bytes.restype = sz
     L.v2ce_convn_dgrad.argtypes = [vp, vp, vp] + [i32] * 7 + [vp, vp, vp, sz, i32, vp]
     L.v2ce_convn_dgrad.restype = ctypes.c_int
+    L.v2ce_convc_wgrad_workspace_bytes.argtypes = [i32] * 8
+    L.v2ce_convc_wgrad_workspace_bytes.restype = sz
+    L.v2ce_convc_wgrad.argtypes = [vp, vp, vp] + [i32] * 7 + [vp, vp, vp, sz, i32, vp]
+    L.v2ce_convc_wgrad.restype = ctypes.c_int
+    L.v2ce_convc_dgrad_workspace_bytes.argtypes = [i32] * 8
+    L.v2ce_convc_dgrad_workspace_bytes.restype = sz
+    L.v2ce_convc_dgrad.argtypes = [vp, vp, vp] + [i32] * 7 + [vp, vp, vp, sz, i32, vp]
+    L.v2ce_convc_dgrad.restype = ctypes.c_int
     L.v2ce_convupn_wgrad_workspace_bytes.argtypes = [i32] * 10
     L.v2ce_convupn_wgrad_workspace_bytes.restype = sz
     L.v2ce_convupn_wgrad.argtypes = [vp, vp, vp, vp] + [i32] * 9 + [vp, vp, vp, vp, sz, i32, vp]

@@ -970,6 +970,25 @@ class V2ce3d(nn.Module):
         return out
 
     @torch.no_grad()
+    def forward_dec1_inputs(self, x: torch.Tensor):
+        """x [B,L,2,H,W] -> (t1, res1, s2, x1): the two tensors the conv2 launch of ``UNet.decoders[1]`` reads -- t1 =
+        relu(bn1(conv1(.))), its input, and res1 = bn_d(conv_d(.)), that block's shortcut branch, both 128 channels at a
+        quarter of the resolution, [B,L,8,H00,pitch00,16] -- s2, the skip tensor of ``UNet.decoders[2]`` (64 channels at half
+        the resolution, [B,L,4,H0,pitch0,16]), and x1, the last decoder block's skip tensor (32 channels,
+        [B,L,2,H,pitch,16]); all channels-last-16 with the logical width in ``.lw``, without gradient (dec1_conv.py:
+        ``Dec1Conv`` turns the pair into ``forward_dec2_sources``'s h1).  In ``f16x2`` that block's shortcut normally rides in
+        conv2's K loop and res1 never exists: this accessor makes conv1's launch and the shortcut's own 1x1x1 launch
+        instead.  Everything in front of the block runs exactly as in ``forward_dec2_sources`` -- the same spectral-norm power
+        iteration (one per call, every layer's included), range-guard policy and precision."""
+        if len(self.UNet.decoders) < 3:
+            raise ValueError("the model has fewer than 3 decoders")
+        out = self._guarded_forward(x, False, features="dec1")
+        for a in out:                   # the range slots are views of a table the next call clears: keep this call's values
+            if hasattr(a, "absmax"):
+                a.absmax = a.absmax.clone()
+        return out
+
+    @torch.no_grad()
     def forward_dec2_sources(self, x: torch.Tensor):
         """x [B,L,2,H,W] -> (h1, s2, x1): the two tensors the decoder in front of the last one (``UNet.decoders[2]``) reads --
         h1, the output of ``UNet.decoders[1]`` (128 channels at a quarter of the resolution, [B,L,8,H00,pitch00,16]), which the
@@ -1032,8 +1051,9 @@ class V2ce3d(nn.Module):
         block and return the two tensors it reads (forward_tail_sources); features="dec2": stop in front of conv2 of the decoder before
         it and return that launch's two inputs and the last block's skip tensor (forward_dec2_inputs); features="dec2_normed": the same
         launches without the BatchNorms' affine parts and the relu (forward_dec2_normed); features="dec2_sources": stop in front of
-        that decoder and return the two tensors it reads and the last block's skip tensor (forward_dec2_sources); the default
-        launches are today's."""
+        that decoder and return the two tensors it reads and the last block's skip tensor (forward_dec2_sources); features="dec1": stop
+        in front of conv2 of UNet.decoders[1] and return that launch's two inputs and the skip tensors of the two blocks behind it
+        (forward_dec1_inputs); the default launches are today's."""
         if self._prep is None:
             self._prepare()
         P, U = self._prep, self.UNet
@@ -1068,6 +1088,11 @@ class V2ce3d(nn.Module):
         fuse = P["pred_fused"] if not (return_intermediates or features) else None
         for i, (blk, skip) in enumerate(zip(U.decoders, reversed(skips))):       # :357-365
             last = i == len(U.decoders) - 1
+            if features == "dec1" and i == len(U.decoders) - 3:
+                later = list(reversed(skips))[i + 1:i + 3]
+                h = self._block_inputs_unfused(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4]))) + \
+                    tuple(later)
+                break
             if features == "dec2" and i == len(U.decoders) - 2:
                 nxt = list(reversed(skips))[i + 1]
                 h = self._block_inputs_unfused(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4]))) + (nxt,)
@@ -1090,7 +1115,7 @@ class V2ce3d(nn.Module):
             h = self._block(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])),
                             pred=fuse if last else None)
             inter[f"dec{i}"] = self.to_planar(h) if return_intermediates else None
-        if features in ("tail", "normed", "sources", "dec2", "dec2_normed", "dec2_sources"):
+        if features in ("tail", "normed", "sources", "dec2", "dec2_normed", "dec2_sources", "dec1"):
             out = tuple(a if getattr(a, "c16", False) else self.to_c16(a) for a in h)
         elif features:
             # (the exact-f32 kernels produce planar tensors: one copy into the layout the head kernels take)
