@@ -5,16 +5,19 @@
 
 The trunk is frozen, so its output -- the 32-channel features in front of ``UNet.pred`` -- is computed once per window
 (``V2ce3d.forward_features``) and every step is ``PredHead`` -> ``losses.calculate_loss`` -> ``backward()`` -> one
-``torch.optim`` step on the head's 660 parameters.  ``v2ce_finetune.py`` is the command line (``main`` below).
+``torch.optim`` step on the head's 660 parameters.  The deeper fits (``fit_tail`` ... ``fit_dec1_conv``) train one more
+layer each; ``STAGES`` lists them and ``_fit`` is the loop they share.  ``v2ce_finetune.py`` is the command line (``main``
+below).
 """
 from __future__ import annotations
 
 import argparse
+import importlib
 import json
 import logging
 import os
 import os.path as op
-from typing import List, Sequence
+from typing import List, NamedTuple, Sequence
 
 import numpy as np
 import torch
@@ -40,6 +43,136 @@ def _windows(image_units, gt_voxels):
     return list(zip(xs, gs))
 
 
+class Stage(NamedTuple):
+    """One training depth.  ``groups``: the parameter groups the stage adds to the shallower ones', each {name: (role,
+    attributes)} (an attribute that is None on the layer, a shortcut without bias, is left out).  ``accessor``: the
+    ``V2ce3d`` method whose tensors a fit of this depth caches.  ``layers``: every layer behind the cached tensors but the
+    head, shallowest first, as (role, "module.Class"); a ``DecoderBlock`` of role r fills the roles r.convs, r.norms and
+    r.conv.  The layers are built and written back in this order and chained in the reverse one: each takes the first
+    two tensors of the list (the cached ones at first) and puts its output, one tensor or a pair, in their place; the
+    head takes the one that is left."""
+    name: str
+    choice: str                 # the command line's --train value
+    groups: dict
+    accessor: str
+    layers: tuple
+
+
+_LAST = (("last.conv", "last_conv.LastConv"), ("last.norms", "last_conv.TailNorms"), ("last.convs", "last_block.TailConvs"))
+_BLOCK = ("last", "last_block.LastBlock")
+_CONV2 = lambda role: (role, ("weight_bar",))
+_BN = lambda role, bn="bn": (role, (bn + "_weight", bn + "_bias"))
+_SHORT = lambda role: (role, ("short_weight", "short_bias"))
+
+STAGES = (
+    Stage("head", "head", {"pred": ("head", ("weight", "bias"))}, "forward_features", ()),
+    Stage("tail", "tail", {"conv2": _CONV2("last.conv"), "bn2": _BN("last.conv")}, "forward_tail_inputs", _LAST[:1]),
+    Stage("tail_norms", "tail_norms", {"bn1": _BN("last.norms", "bn1"), "bnd": _BN("last.norms", "bnd")},
+          "forward_tail_normed", _LAST[:2]),
+    Stage("last_block", "last_block", {"conv1": _CONV2("last.convs"), "convd": _SHORT("last.convs")},
+          "forward_tail_sources", _LAST),
+    Stage("dec2_conv", "dec2_conv2", {"dec2_conv2": _CONV2("dec2.conv"), "dec2_bn2": _BN("dec2.conv")},
+          "forward_dec2_inputs", (_BLOCK, ("dec2.conv", "dec2_conv.Dec2Conv"))),
+    Stage("dec2_block", "dec2_block",
+          {"dec2_conv1": _CONV2("dec2.convs"), "dec2_convd": _SHORT("dec2.convs"), "dec2_bn1": _BN("dec2.norms", "bn1"),
+           "dec2_bnd": _BN("dec2.norms", "bnd")},
+          "forward_dec2_sources", (_BLOCK, ("dec2", "dec2_block.Dec2Block"))),
+    Stage("dec1_conv", "dec1_conv2", {"dec1_conv2": _CONV2("dec1.conv"), "dec1_bn2": _BN("dec1.conv")},
+          "forward_dec1_inputs", (_BLOCK, ("dec2", "dec2_block.Dec2BlockThrough"), ("dec1.conv", "dec1_conv.Dec1Conv"))),
+)
+
+
+def _depth(train, allowed) -> int:
+    """-> the index in ``STAGES`` of the deepest stage that has a group in ``train``: the depth to which layers are built.
+    ``train`` must be a non-empty subset of ``allowed`` without repeats."""
+    train = tuple(train)
+    if not train or any(g not in allowed for g in train) or len(set(train)) != len(train):
+        raise ValueError(f"train must be a non-empty subset of {allowed}, got {train}")
+    return max(i for i, stage in enumerate(STAGES) if any(g in stage.groups for g in train))
+
+
+def _build(model, stage):
+    """-> (the stage's layers in the order of ``stage.layers``, {role: layer} with the head's)."""
+    from .decoder_block import DecoderBlock
+    head = PredHead.from_model(model)
+    layers, roles = [], {"head": head}
+    for role, path in stage.layers:
+        module, cls = path.split(".")
+        layer = getattr(importlib.import_module("." + module, __package__), cls).from_model(model)
+        layers.append(layer)
+        if isinstance(layer, DecoderBlock):
+            roles.update({f"{role}.convs": layer.convs, f"{role}.norms": layer.norms, f"{role}.conv": layer.conv})
+        else:
+            roles[role] = layer
+    return head, layers, roles
+
+
+def _fit(model, image_units, gt_voxels, *, allowed, train, loss, steps, lr, optimizer, cache_bytes, loss_options) -> List[dict]:
+    """The loop of every ``fit_*``: train the groups ``train`` (a subset of ``allowed``) at the depth of the deepest one.
+
+    The tensors of the depth's accessor are computed once per window and kept while the kept ones fit in ``cache_bytes``; a
+    window beyond the budget is recomputed at each of its steps.  Every such pass starts from the spectral-norm state the
+    model had on entry, so a window's tensors do not depend on whether they were cached.  Every step is the depth's layers
+    -> ``PredHead`` -> ``losses.calculate_loss`` -> ``backward()`` -> one optimizer step on the parameters of ``train``, in
+    its order; every group of the depth has ``requires_grad`` set, to whether it is trained.  On return the model's
+    spectral-norm u / v and call counter are restored, then every layer built writes its tensors back.
+    (``loss_options`` is a dict, not ``**``: a stray keyword of a caller stays a loss option.)"""
+    depth = _depth(train, allowed)
+    train = tuple(train)
+    loss = losses.check_loss_names(loss)
+    if optimizer not in ("adam", "sgd"):
+        raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
+    if int(steps) < 0:
+        raise ValueError(f"steps must be >= 0, got {steps}")
+    windows = _windows(image_units, gt_voxels)
+    stage = STAGES[depth]
+    head, layers, roles = _build(model, stage)
+    groups = {g: [p for p in (getattr(roles[role], a) for a in attrs) if p is not None]
+              for s in STAGES[:depth + 1] for g, (role, attrs) in s.groups.items()}
+    for g, ps in groups.items():
+        for p in ps:
+            p.requires_grad_(g in train)
+    opt = (torch.optim.Adam if optimizer == "adam" else torch.optim.SGD)([p for g in train for p in groups[g]], lr=lr)
+    snap = model.sn_snapshot()
+    cache, used = {}, 0
+
+    def inputs(i):
+        nonlocal used
+        if i in cache:
+            return cache[i]
+        model.sn_restore(snap)
+        out = getattr(model, stage.accessor)(windows[i][0])
+        out = out if isinstance(out, tuple) else (out,)
+        nb = sum(a.numel() for a in out) * 4
+        if used + nb <= cache_bytes:
+            cache[i], used = out, used + nb
+        return out
+
+    history = []
+    try:
+        for k in range(int(steps)):
+            i = k % len(windows)
+            opt.zero_grad(set_to_none=True)
+            args = list(inputs(i))
+            for layer in reversed(layers):
+                out = layer(args[0], args[1])
+                args[:2] = out if isinstance(out, tuple) else (out,)
+            pred = head(*args)
+            total, d = losses.calculate_loss(pred, windows[i][1].contiguous(), loss=loss, **loss_options)
+            total.backward()
+            opt.step()
+            history.append({"loss": float(total.detach()), "loss_dict": {n: float(v) for n, v in d.items()}})
+    finally:
+        model.sn_restore(snap)
+    guards = [float(layer.guard) for layer in roles.values() if hasattr(layer, "guard")]
+    if guards and model.precision == "f16x2" and max(guards) > model.RANGE_GUARD_LIMIT:
+        logger.warning(f"split-half range guard of the trained convolution{'s' if len(guards) > 1 else ''}: bound "
+                       f"{max(guards):.3e} > {model.RANGE_GUARD_LIMIT:.1e}; fit with precision='f32'")
+    for layer in [head] + layers:
+        layer.write_back(model)
+    return history
+
+
 def fit_head(model, image_units, gt_voxels, *, loss: Sequence[str] = losses.DEFAULT_LOSS, steps: int, lr: float,
              optimizer: str = "adam", cache_bytes: int = DEFAULT_CACHE_BYTES, **loss_options) -> List[dict]:
     """Fit ``model.UNet.pred`` to ground-truth voxels with the rest of the network frozen.
@@ -55,42 +188,8 @@ def fit_head(model, image_units, gt_voxels, *, loss: Sequence[str] = losses.DEFA
     Returns the history: per step ``{"loss": float, "loss_dict": {name: float}}``, the values before that step's
     update.  On return the model differs from its state on entry in ``UNet.pred.conv3d.weight`` and ``.bias`` only:
     the spectral-norm u / v and the call counter are restored."""
-    loss = losses.check_loss_names(loss)
-    if optimizer not in ("adam", "sgd"):
-        raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
-    if int(steps) < 0:
-        raise ValueError(f"steps must be >= 0, got {steps}")
-    windows = _windows(image_units, gt_voxels)
-    head = PredHead.from_model(model)
-    opt = (torch.optim.Adam if optimizer == "adam" else torch.optim.SGD)(head.parameters(), lr=lr)
-    snap = model.sn_snapshot()
-    cache, used = {}, 0
-
-    def features(i):
-        nonlocal used
-        if i in cache:
-            return cache[i]
-        model.sn_restore(snap)
-        f = model.forward_features(windows[i][0])
-        nb = f.numel() * 4
-        if used + nb <= cache_bytes:
-            cache[i], used = f, used + nb
-        return f
-
-    history = []
-    try:
-        for k in range(int(steps)):
-            i = k % len(windows)
-            opt.zero_grad(set_to_none=True)
-            pred = head(features(i))
-            total, d = losses.calculate_loss(pred, windows[i][1].contiguous(), loss=loss, **loss_options)
-            total.backward()
-            opt.step()
-            history.append({"loss": float(total.detach()), "loss_dict": {n: float(v) for n, v in d.items()}})
-    finally:
-        model.sn_restore(snap)
-    head.write_back(model)
-    return history
+    return _fit(model, image_units, gt_voxels, allowed=("pred",), train=("pred",), loss=loss, steps=steps, lr=lr,
+                optimizer=optimizer, cache_bytes=cache_bytes, loss_options=loss_options)
 
 
 TAIL_GROUPS = ("pred", "conv2", "bn2")
@@ -106,66 +205,16 @@ def fit_tail(model, image_units, gt_voxels, *, train: Sequence[str] = TAIL_GROUP
     convolution's ``weight_bar``), 'bn2' (the BatchNorm's weight and bias; its statistics stay frozen).  The other
     arguments and the returned history are those of ``fit_head``.
 
-    The two inputs of the convolution (``V2ce3d.forward_tail_inputs``) are computed once per window and kept while the
-    kept ones fit in ``cache_bytes``; every step is ``LastConv`` -> ``PredHead`` -> ``losses.calculate_loss`` ->
-    ``backward()`` -> one optimizer step.  As in the reference, every forward of the trained convolution advances its
-    spectral-norm u / v by one power iteration.  With neither 'conv2' nor 'bn2' in ``train`` the features in front of the
-    head are constant and this is ``fit_head``, step for step.
+    The two inputs of the convolution (``V2ce3d.forward_tail_inputs``) are cached per window; every step is ``LastConv`` ->
+    ``PredHead`` -> the loss.  As in the reference, every forward of the trained convolution advances its spectral-norm
+    u / v by one power iteration.  With neither 'conv2' nor 'bn2' in ``train`` the features in front of the head are
+    constant and this is ``fit_head``, step for step.
 
     On return the model differs from its state on entry in the trained tensors and in conv2's ``weight_u`` /
     ``weight_v``, which keep the iterations the fit applied; the other eleven spectral-norm layers and the call counter
     are restored."""
-    from .last_conv import LastConv
-    train = tuple(train)
-    if not train or any(g not in TAIL_GROUPS for g in train) or len(set(train)) != len(train):
-        raise ValueError(f"train must be a non-empty subset of {TAIL_GROUPS}, got {train}")
-    if not ("conv2" in train or "bn2" in train):
-        return fit_head(model, image_units, gt_voxels, loss=loss, steps=steps, lr=lr, optimizer=optimizer,
-                        cache_bytes=cache_bytes, **loss_options)
-    loss = losses.check_loss_names(loss)
-    if optimizer not in ("adam", "sgd"):
-        raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
-    if int(steps) < 0:
-        raise ValueError(f"steps must be >= 0, got {steps}")
-    windows = _windows(image_units, gt_voxels)
-    head, conv = PredHead.from_model(model), LastConv.from_model(model)
-    groups = {"pred": [head.weight, head.bias], "conv2": [conv.weight_bar], "bn2": [conv.bn_weight, conv.bn_bias]}
-    for g, ps in groups.items():
-        for p in ps:
-            p.requires_grad_(g in train)
-    opt = (torch.optim.Adam if optimizer == "adam" else torch.optim.SGD)([p for g in train for p in groups[g]], lr=lr)
-    snap = model.sn_snapshot()
-    cache, used = {}, 0
-
-    def inputs(i):
-        nonlocal used
-        if i in cache:
-            return cache[i]
-        model.sn_restore(snap)
-        t, res = model.forward_tail_inputs(windows[i][0])
-        nb = (t.numel() + res.numel()) * 4
-        if used + nb <= cache_bytes:
-            cache[i], used = (t, res), used + nb
-        return t, res
-
-    history = []
-    try:
-        for k in range(int(steps)):
-            i = k % len(windows)
-            opt.zero_grad(set_to_none=True)
-            pred = head(conv(*inputs(i)))
-            total, d = losses.calculate_loss(pred, windows[i][1].contiguous(), loss=loss, **loss_options)
-            total.backward()
-            opt.step()
-            history.append({"loss": float(total.detach()), "loss_dict": {n: float(v) for n, v in d.items()}})
-    finally:
-        model.sn_restore(snap)
-    if model.precision == "f16x2" and float(conv.guard) > model.RANGE_GUARD_LIMIT:
-        logger.warning(f"split-half range guard of the trained convolution: bound {float(conv.guard):.3e} > "
-                       f"{model.RANGE_GUARD_LIMIT:.1e}; fit with precision='f32'")
-    head.write_back(model)
-    conv.write_back(model)
-    return history
+    return _fit(model, image_units, gt_voxels, allowed=TAIL_GROUPS, train=train, loss=loss, steps=steps, lr=lr,
+                optimizer=optimizer, cache_bytes=cache_bytes, loss_options=loss_options)
 
 
 TAIL_NORM_GROUPS = TAIL_GROUPS + ("bn1", "bnd")
@@ -184,65 +233,13 @@ def fit_tail_norms(model, image_units, gt_voxels, *, train: Sequence[str] = TAIL
     step.
 
     The normalised, pre-affine pair in front of the two BatchNorms' affine parts (``V2ce3d.forward_tail_normed``) is
-    computed once per window and kept while the kept ones fit in ``cache_bytes``; every step is ``TailNorms`` ->
-    ``LastConv`` -> ``PredHead`` -> ``losses.calculate_loss`` -> ``backward()`` -> one optimizer step.
+    cached per window; every step is ``TailNorms`` -> ``LastConv`` -> ``PredHead`` -> the loss.
 
     On return the model differs from its state on entry in the trained tensors and in conv2's ``weight_u`` /
     ``weight_v``, which keep the iterations the fit applied; the other eleven spectral-norm layers and the call counter
     are restored."""
-    from .last_conv import LastConv, TailNorms
-    train = tuple(train)
-    if not train or any(g not in TAIL_NORM_GROUPS for g in train) or len(set(train)) != len(train):
-        raise ValueError(f"train must be a non-empty subset of {TAIL_NORM_GROUPS}, got {train}")
-    if not ("bn1" in train or "bnd" in train):
-        return fit_tail(model, image_units, gt_voxels, train=train, loss=loss, steps=steps, lr=lr, optimizer=optimizer,
-                        cache_bytes=cache_bytes, **loss_options)
-    loss = losses.check_loss_names(loss)
-    if optimizer not in ("adam", "sgd"):
-        raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
-    if int(steps) < 0:
-        raise ValueError(f"steps must be >= 0, got {steps}")
-    windows = _windows(image_units, gt_voxels)
-    head, conv, norms = PredHead.from_model(model), LastConv.from_model(model), TailNorms.from_model(model)
-    groups = {"pred": [head.weight, head.bias], "conv2": [conv.weight_bar], "bn2": [conv.bn_weight, conv.bn_bias],
-              "bn1": [norms.bn1_weight, norms.bn1_bias], "bnd": [norms.bnd_weight, norms.bnd_bias]}
-    for g, ps in groups.items():
-        for p in ps:
-            p.requires_grad_(g in train)
-    opt = (torch.optim.Adam if optimizer == "adam" else torch.optim.SGD)([p for g in train for p in groups[g]], lr=lr)
-    snap = model.sn_snapshot()
-    cache, used = {}, 0
-
-    def inputs(i):
-        nonlocal used
-        if i in cache:
-            return cache[i]
-        model.sn_restore(snap)
-        z1, zd = model.forward_tail_normed(windows[i][0])
-        nb = (z1.numel() + zd.numel()) * 4
-        if used + nb <= cache_bytes:
-            cache[i], used = (z1, zd), used + nb
-        return z1, zd
-
-    history = []
-    try:
-        for k in range(int(steps)):
-            i = k % len(windows)
-            opt.zero_grad(set_to_none=True)
-            pred = head(conv(*norms(*inputs(i))))
-            total, d = losses.calculate_loss(pred, windows[i][1].contiguous(), loss=loss, **loss_options)
-            total.backward()
-            opt.step()
-            history.append({"loss": float(total.detach()), "loss_dict": {n: float(v) for n, v in d.items()}})
-    finally:
-        model.sn_restore(snap)
-    if model.precision == "f16x2" and float(conv.guard) > model.RANGE_GUARD_LIMIT:
-        logger.warning(f"split-half range guard of the trained convolution: bound {float(conv.guard):.3e} > "
-                       f"{model.RANGE_GUARD_LIMIT:.1e}; fit with precision='f32'")
-    head.write_back(model)
-    conv.write_back(model)
-    norms.write_back(model)
-    return history
+    return _fit(model, image_units, gt_voxels, allowed=TAIL_NORM_GROUPS, train=train, loss=loss, steps=steps, lr=lr,
+                optimizer=optimizer, cache_bytes=cache_bytes, loss_options=loss_options)
 
 
 LAST_BLOCK_GROUPS = TAIL_NORM_GROUPS + ("conv1", "convd")
@@ -260,73 +257,15 @@ def fit_last_block(model, image_units, gt_voxels, *, train: Sequence[str] = LAST
     bias).  The other arguments and the returned history are those of ``fit_tail_norms``.  With neither 'conv1' nor
     'convd' in ``train`` this is ``fit_tail_norms`` with the same arguments, step for step.
 
-    The block's two sources (``V2ce3d.forward_tail_sources``) are computed once per window and kept while the kept ones
-    fit in ``cache_bytes``; every step is ``TailConvs`` -> ``TailNorms`` -> ``LastConv`` -> ``PredHead`` ->
-    ``losses.calculate_loss`` -> ``backward()`` -> one optimizer step.  As in the reference, every forward of a trained
+    The block's two sources (``V2ce3d.forward_tail_sources``) are cached per window; every step is ``TailConvs`` ->
+    ``TailNorms`` -> ``LastConv`` -> ``PredHead`` -> the loss.  As in the reference, every forward of a trained
     convolution advances its spectral-norm u / v by one power iteration.
 
     On return the model differs from its state on entry in the trained tensors and in the ``weight_u`` / ``weight_v`` of
     the block's conv1 and conv2, which keep the iterations the fit applied; the other ten spectral-norm layers and the
     call counter are restored."""
-    from .last_block import TailConvs
-    from .last_conv import LastConv, TailNorms
-    train = tuple(train)
-    if not train or any(g not in LAST_BLOCK_GROUPS for g in train) or len(set(train)) != len(train):
-        raise ValueError(f"train must be a non-empty subset of {LAST_BLOCK_GROUPS}, got {train}")
-    if not ("conv1" in train or "convd" in train):
-        return fit_tail_norms(model, image_units, gt_voxels, train=train, loss=loss, steps=steps, lr=lr, optimizer=optimizer,
-                              cache_bytes=cache_bytes, **loss_options)
-    loss = losses.check_loss_names(loss)
-    if optimizer not in ("adam", "sgd"):
-        raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
-    if int(steps) < 0:
-        raise ValueError(f"steps must be >= 0, got {steps}")
-    windows = _windows(image_units, gt_voxels)
-    head, conv, norms = PredHead.from_model(model), LastConv.from_model(model), TailNorms.from_model(model)
-    convs = TailConvs.from_model(model)
-    groups = {"pred": [head.weight, head.bias], "conv2": [conv.weight_bar], "bn2": [conv.bn_weight, conv.bn_bias],
-              "bn1": [norms.bn1_weight, norms.bn1_bias], "bnd": [norms.bnd_weight, norms.bnd_bias],
-              "conv1": [convs.weight_bar],
-              "convd": [convs.short_weight] + ([convs.short_bias] if convs.short_bias is not None else [])}
-    for g, ps in groups.items():
-        for p in ps:
-            p.requires_grad_(g in train)
-    opt = (torch.optim.Adam if optimizer == "adam" else torch.optim.SGD)([p for g in train for p in groups[g]], lr=lr)
-    snap = model.sn_snapshot()
-    cache, used = {}, 0
-
-    def inputs(i):
-        nonlocal used
-        if i in cache:
-            return cache[i]
-        model.sn_restore(snap)
-        x0, x1 = model.forward_tail_sources(windows[i][0])
-        nb = (x0.numel() + x1.numel()) * 4
-        if used + nb <= cache_bytes:
-            cache[i], used = (x0, x1), used + nb
-        return x0, x1
-
-    history = []
-    try:
-        for k in range(int(steps)):
-            i = k % len(windows)
-            opt.zero_grad(set_to_none=True)
-            pred = head(conv(*norms(*convs(*inputs(i)))))
-            total, d = losses.calculate_loss(pred, windows[i][1].contiguous(), loss=loss, **loss_options)
-            total.backward()
-            opt.step()
-            history.append({"loss": float(total.detach()), "loss_dict": {n: float(v) for n, v in d.items()}})
-    finally:
-        model.sn_restore(snap)
-    bound = max(float(conv.guard), float(convs.guard))
-    if model.precision == "f16x2" and bound > model.RANGE_GUARD_LIMIT:
-        logger.warning(f"split-half range guard of the trained convolutions: bound {bound:.3e} > "
-                       f"{model.RANGE_GUARD_LIMIT:.1e}; fit with precision='f32'")
-    head.write_back(model)
-    conv.write_back(model)
-    norms.write_back(model)
-    convs.write_back(model)
-    return history
+    return _fit(model, image_units, gt_voxels, allowed=LAST_BLOCK_GROUPS, train=train, loss=loss, steps=steps, lr=lr,
+                optimizer=optimizer, cache_bytes=cache_bytes, loss_options=loss_options)
 
 
 DEC2_CONV_GROUPS = LAST_BLOCK_GROUPS + ("dec2_conv2", "dec2_bn2")
@@ -345,75 +284,16 @@ def fit_dec2_conv(model, image_units, gt_voxels, *, train: Sequence[str] = DEC2_
     other arguments and the returned history are those of ``fit_last_block``.  With neither 'dec2_conv2' nor 'dec2_bn2' in
     ``train`` this is ``fit_last_block`` with the same arguments, step for step.
 
-    The two inputs of the convolution and the last block's skip tensor (``V2ce3d.forward_dec2_inputs``) are computed once
-    per window and kept while the kept ones fit in ``cache_bytes``; every step is ``Dec2Conv`` -> ``LastBlock`` ->
-    ``PredHead`` -> ``losses.calculate_loss`` -> ``backward()`` -> one optimizer step.  The last block is asked for the
+    The two inputs of the convolution and the last block's skip tensor (``V2ce3d.forward_dec2_inputs``) are cached per
+    window; every step is ``Dec2Conv`` -> ``LastBlock`` -> ``PredHead`` -> the loss.  The last block is asked for the
     gradient of its source alone: the skip tensor requires none.  As in the reference, every forward of a trained
     convolution advances its spectral-norm u / v by one power iteration.
 
     On return the model differs from its state on entry in the trained tensors and in the ``weight_u`` / ``weight_v`` of
     dec2's conv2 and of the last block's conv1 and conv2, which keep the iterations the fit applied; the other nine
     spectral-norm layers and the call counter are restored."""
-    from .dec2_conv import Dec2Conv
-    from .last_block import LastBlock
-    train = tuple(train)
-    if not train or any(g not in DEC2_CONV_GROUPS for g in train) or len(set(train)) != len(train):
-        raise ValueError(f"train must be a non-empty subset of {DEC2_CONV_GROUPS}, got {train}")
-    if not ("dec2_conv2" in train or "dec2_bn2" in train):
-        return fit_last_block(model, image_units, gt_voxels, train=train, loss=loss, steps=steps, lr=lr, optimizer=optimizer,
-                              cache_bytes=cache_bytes, **loss_options)
-    loss = losses.check_loss_names(loss)
-    if optimizer not in ("adam", "sgd"):
-        raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
-    if int(steps) < 0:
-        raise ValueError(f"steps must be >= 0, got {steps}")
-    windows = _windows(image_units, gt_voxels)
-    head, block, dec2 = PredHead.from_model(model), LastBlock.from_model(model), Dec2Conv.from_model(model)
-    convs, norms, conv = block.convs, block.norms, block.conv
-    groups = {"pred": [head.weight, head.bias], "conv2": [conv.weight_bar], "bn2": [conv.bn_weight, conv.bn_bias],
-              "bn1": [norms.bn1_weight, norms.bn1_bias], "bnd": [norms.bnd_weight, norms.bnd_bias],
-              "conv1": [convs.weight_bar],
-              "convd": [convs.short_weight] + ([convs.short_bias] if convs.short_bias is not None else []),
-              "dec2_conv2": [dec2.weight_bar], "dec2_bn2": [dec2.bn_weight, dec2.bn_bias]}
-    for g, ps in groups.items():
-        for p in ps:
-            p.requires_grad_(g in train)
-    opt = (torch.optim.Adam if optimizer == "adam" else torch.optim.SGD)([p for g in train for p in groups[g]], lr=lr)
-    snap = model.sn_snapshot()
-    cache, used = {}, 0
-
-    def inputs(i):
-        nonlocal used
-        if i in cache:
-            return cache[i]
-        model.sn_restore(snap)
-        trio = model.forward_dec2_inputs(windows[i][0])
-        nb = sum(a.numel() for a in trio) * 4
-        if used + nb <= cache_bytes:
-            cache[i], used = trio, used + nb
-        return trio
-
-    history = []
-    try:
-        for k in range(int(steps)):
-            i = k % len(windows)
-            opt.zero_grad(set_to_none=True)
-            t2, res2, x1 = inputs(i)
-            pred = head(block(dec2(t2, res2), x1))
-            total, d = losses.calculate_loss(pred, windows[i][1].contiguous(), loss=loss, **loss_options)
-            total.backward()
-            opt.step()
-            history.append({"loss": float(total.detach()), "loss_dict": {n: float(v) for n, v in d.items()}})
-    finally:
-        model.sn_restore(snap)
-    bound = max(float(conv.guard), float(convs.guard), float(dec2.guard))
-    if model.precision == "f16x2" and bound > model.RANGE_GUARD_LIMIT:
-        logger.warning(f"split-half range guard of the trained convolutions: bound {bound:.3e} > "
-                       f"{model.RANGE_GUARD_LIMIT:.1e}; fit with precision='f32'")
-    head.write_back(model)
-    block.write_back(model)
-    dec2.write_back(model)
-    return history
+    return _fit(model, image_units, gt_voxels, allowed=DEC2_CONV_GROUPS, train=train, loss=loss, steps=steps, lr=lr,
+                optimizer=optimizer, cache_bytes=cache_bytes, loss_options=loss_options)
 
 
 DEC2_BLOCK_GROUPS = DEC2_CONV_GROUPS + ("dec2_conv1", "dec2_convd", "dec2_bn1", "dec2_bnd")
@@ -432,77 +312,15 @@ def fit_dec2_block(model, image_units, gt_voxels, *, train: Sequence[str] = DEC2
     (weight and bias each; the statistics stay frozen).  The other arguments and the returned history are those of
     ``fit_dec2_conv``.  With none of the four in ``train`` this is ``fit_dec2_conv`` with the same arguments, step for step.
 
-    The block's two sources and the last block's skip tensor (``V2ce3d.forward_dec2_sources``) are computed once per window
-    and kept while the kept ones fit in ``cache_bytes``; every step is ``Dec2Block`` -> ``LastBlock`` -> ``PredHead`` ->
-    ``losses.calculate_loss`` -> ``backward()`` -> one optimizer step.  As in the reference, every forward of a trained
-    convolution advances its spectral-norm u / v by one power iteration.
+    The block's two sources and the last block's skip tensor (``V2ce3d.forward_dec2_sources``) are cached per window;
+    every step is ``Dec2Block`` -> ``LastBlock`` -> ``PredHead`` -> the loss.  As in the reference, every forward of a
+    trained convolution advances its spectral-norm u / v by one power iteration.
 
     On return the model differs from its state on entry in the trained tensors and in the ``weight_u`` / ``weight_v`` of
     the two convolutions of each of the two blocks, which keep the iterations the fit applied; the other eight
     spectral-norm layers and the call counter are restored."""
-    from .dec2_block import Dec2Block
-    from .last_block import LastBlock
-    train = tuple(train)
-    if not train or any(g not in DEC2_BLOCK_GROUPS for g in train) or len(set(train)) != len(train):
-        raise ValueError(f"train must be a non-empty subset of {DEC2_BLOCK_GROUPS}, got {train}")
-    if not any(g in train for g in ("dec2_conv1", "dec2_convd", "dec2_bn1", "dec2_bnd")):
-        return fit_dec2_conv(model, image_units, gt_voxels, train=train, loss=loss, steps=steps, lr=lr, optimizer=optimizer,
-                             cache_bytes=cache_bytes, **loss_options)
-    loss = losses.check_loss_names(loss)
-    if optimizer not in ("adam", "sgd"):
-        raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
-    if int(steps) < 0:
-        raise ValueError(f"steps must be >= 0, got {steps}")
-    windows = _windows(image_units, gt_voxels)
-    head, block, dec2 = PredHead.from_model(model), LastBlock.from_model(model), Dec2Block.from_model(model)
-    convs, norms, conv = block.convs, block.norms, block.conv
-    groups = {"pred": [head.weight, head.bias], "conv2": [conv.weight_bar], "bn2": [conv.bn_weight, conv.bn_bias],
-              "bn1": [norms.bn1_weight, norms.bn1_bias], "bnd": [norms.bnd_weight, norms.bnd_bias],
-              "conv1": [convs.weight_bar],
-              "convd": [convs.short_weight] + ([convs.short_bias] if convs.short_bias is not None else []),
-              "dec2_conv2": [dec2.conv.weight_bar], "dec2_bn2": [dec2.conv.bn_weight, dec2.conv.bn_bias],
-              "dec2_conv1": [dec2.convs.weight_bar],
-              "dec2_convd": [dec2.convs.short_weight] + ([dec2.convs.short_bias] if dec2.convs.short_bias is not None else []),
-              "dec2_bn1": [dec2.norms.bn1_weight, dec2.norms.bn1_bias], "dec2_bnd": [dec2.norms.bnd_weight, dec2.norms.bnd_bias]}
-    for g, ps in groups.items():
-        for p in ps:
-            p.requires_grad_(g in train)
-    opt = (torch.optim.Adam if optimizer == "adam" else torch.optim.SGD)([p for g in train for p in groups[g]], lr=lr)
-    snap = model.sn_snapshot()
-    cache, used = {}, 0
-
-    def inputs(i):
-        nonlocal used
-        if i in cache:
-            return cache[i]
-        model.sn_restore(snap)
-        trio = model.forward_dec2_sources(windows[i][0])
-        nb = sum(a.numel() for a in trio) * 4
-        if used + nb <= cache_bytes:
-            cache[i], used = trio, used + nb
-        return trio
-
-    history = []
-    try:
-        for k in range(int(steps)):
-            i = k % len(windows)
-            opt.zero_grad(set_to_none=True)
-            h1, s2, x1 = inputs(i)
-            pred = head(block(dec2(h1, s2), x1))
-            total, d = losses.calculate_loss(pred, windows[i][1].contiguous(), loss=loss, **loss_options)
-            total.backward()
-            opt.step()
-            history.append({"loss": float(total.detach()), "loss_dict": {n: float(v) for n, v in d.items()}})
-    finally:
-        model.sn_restore(snap)
-    bound = max(float(conv.guard), float(convs.guard), float(dec2.conv.guard), float(dec2.convs.guard))
-    if model.precision == "f16x2" and bound > model.RANGE_GUARD_LIMIT:
-        logger.warning(f"split-half range guard of the trained convolutions: bound {bound:.3e} > "
-                       f"{model.RANGE_GUARD_LIMIT:.1e}; fit with precision='f32'")
-    head.write_back(model)
-    block.write_back(model)
-    dec2.write_back(model)
-    return history
+    return _fit(model, image_units, gt_voxels, allowed=DEC2_BLOCK_GROUPS, train=train, loss=loss, steps=steps, lr=lr,
+                optimizer=optimizer, cache_bytes=cache_bytes, loss_options=loss_options)
 
 
 DEC1_CONV_GROUPS = DEC2_BLOCK_GROUPS + ("dec1_conv2", "dec1_bn2")
@@ -522,81 +340,15 @@ def fit_dec1_conv(model, image_units, gt_voxels, *, train: Sequence[str] = DEC1_
     arguments, step for step.
 
     The convolution's two inputs and the skip tensors of the two blocks behind it (``V2ce3d.forward_dec1_inputs``) are
-    computed once per window and kept while the kept ones fit in ``cache_bytes``; every step is ``Dec1Conv`` ->
-    ``Dec2BlockThrough`` (asked for the gradient of ``h1`` alone) -> ``LastBlock`` -> ``PredHead`` ->
-    ``losses.calculate_loss`` -> ``backward()`` -> one optimizer step.  As in the reference, every forward of a trained
-    convolution advances its spectral-norm u / v by one power iteration.
+    cached per window; every step is ``Dec1Conv`` -> ``Dec2BlockThrough`` (asked for the gradient of ``h1`` alone) ->
+    ``LastBlock`` -> ``PredHead`` -> the loss.  As in the reference, every forward of a trained convolution advances its
+    spectral-norm u / v by one power iteration.
 
     On return the model differs from its state on entry in the trained tensors and in the ``weight_u`` / ``weight_v`` of
     ``UNet.decoders[1].conv2`` and of the two convolutions of each of the two blocks behind it, which keep the iterations
     the fit applied; the other seven spectral-norm layers and the call counter are restored."""
-    from .dec1_conv import Dec1Conv
-    from .dec2_block import Dec2BlockThrough
-    from .last_block import LastBlock
-    train = tuple(train)
-    if not train or any(g not in DEC1_CONV_GROUPS for g in train) or len(set(train)) != len(train):
-        raise ValueError(f"train must be a non-empty subset of {DEC1_CONV_GROUPS}, got {train}")
-    if not any(g in train for g in ("dec1_conv2", "dec1_bn2")):
-        return fit_dec2_block(model, image_units, gt_voxels, train=train, loss=loss, steps=steps, lr=lr, optimizer=optimizer,
-                              cache_bytes=cache_bytes, **loss_options)
-    loss = losses.check_loss_names(loss)
-    if optimizer not in ("adam", "sgd"):
-        raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
-    if int(steps) < 0:
-        raise ValueError(f"steps must be >= 0, got {steps}")
-    windows = _windows(image_units, gt_voxels)
-    head, block, dec2 = PredHead.from_model(model), LastBlock.from_model(model), Dec2BlockThrough.from_model(model)
-    dec1 = Dec1Conv.from_model(model)
-    convs, norms, conv = block.convs, block.norms, block.conv
-    groups = {"pred": [head.weight, head.bias], "conv2": [conv.weight_bar], "bn2": [conv.bn_weight, conv.bn_bias],
-              "bn1": [norms.bn1_weight, norms.bn1_bias], "bnd": [norms.bnd_weight, norms.bnd_bias],
-              "conv1": [convs.weight_bar],
-              "convd": [convs.short_weight] + ([convs.short_bias] if convs.short_bias is not None else []),
-              "dec2_conv2": [dec2.conv.weight_bar], "dec2_bn2": [dec2.conv.bn_weight, dec2.conv.bn_bias],
-              "dec2_conv1": [dec2.convs.weight_bar],
-              "dec2_convd": [dec2.convs.short_weight] + ([dec2.convs.short_bias] if dec2.convs.short_bias is not None else []),
-              "dec2_bn1": [dec2.norms.bn1_weight, dec2.norms.bn1_bias], "dec2_bnd": [dec2.norms.bnd_weight, dec2.norms.bnd_bias],
-              "dec1_conv2": [dec1.weight_bar], "dec1_bn2": [dec1.bn_weight, dec1.bn_bias]}
-    for g, ps in groups.items():
-        for p in ps:
-            p.requires_grad_(g in train)
-    opt = (torch.optim.Adam if optimizer == "adam" else torch.optim.SGD)([p for g in train for p in groups[g]], lr=lr)
-    snap = model.sn_snapshot()
-    cache, used = {}, 0
-
-    def inputs(i):
-        nonlocal used
-        if i in cache:
-            return cache[i]
-        model.sn_restore(snap)
-        four = model.forward_dec1_inputs(windows[i][0])
-        nb = sum(a.numel() for a in four) * 4
-        if used + nb <= cache_bytes:
-            cache[i], used = four, used + nb
-        return four
-
-    history = []
-    try:
-        for k in range(int(steps)):
-            i = k % len(windows)
-            opt.zero_grad(set_to_none=True)
-            t1, res1, s2, x1 = inputs(i)
-            pred = head(block(dec2(dec1(t1, res1), s2), x1))
-            total, d = losses.calculate_loss(pred, windows[i][1].contiguous(), loss=loss, **loss_options)
-            total.backward()
-            opt.step()
-            history.append({"loss": float(total.detach()), "loss_dict": {n: float(v) for n, v in d.items()}})
-    finally:
-        model.sn_restore(snap)
-    bound = max(float(conv.guard), float(convs.guard), float(dec2.conv.guard), float(dec2.convs.guard), float(dec1.guard))
-    if model.precision == "f16x2" and bound > model.RANGE_GUARD_LIMIT:
-        logger.warning(f"split-half range guard of the trained convolutions: bound {bound:.3e} > "
-                       f"{model.RANGE_GUARD_LIMIT:.1e}; fit with precision='f32'")
-    head.write_back(model)
-    block.write_back(model)
-    dec2.write_back(model)
-    dec1.write_back(model)
-    return history
+    return _fit(model, image_units, gt_voxels, allowed=DEC1_CONV_GROUPS, train=train, loss=loss, steps=steps, lr=lr,
+                optimizer=optimizer, cache_bytes=cache_bytes, loss_options=loss_options)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -633,7 +385,7 @@ def build_parser():
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--optimizer", default="adam", choices=("adam", "sgd"))
-    p.add_argument("--train", default="head", choices=("head", "tail", "tail_norms", "last_block", "dec2_conv2", "dec2_block", "dec1_conv2"),
+    p.add_argument("--train", default="head", choices=tuple(stage.choice for stage in STAGES),
                    help="head: UNet.pred alone (fit_head); tail: the last decoder convolution, its bn2 and UNet.pred (fit_tail); "
                         "tail_norms: those and the last decoder block's bn1 and downsample.1 (fit_tail_norms); "
                         "last_block: those and the block's conv1 and shortcut convolution, the whole last decoder block "
@@ -708,8 +460,7 @@ def main(argv=None):
     names = tuple(args.losses) if args.losses else losses.DEFAULT_LOSS
     opts = {k: getattr(args, k) for k in ("ef_type", "add_base_loss", "alpha_pyramid", "alpha_ef", "alpha_efc",
                                           "alpha_match", "alpha_compensation", "alpha_pt", "alpha_norm")}
-    fit = {"head": fit_head, "tail": fit_tail, "tail_norms": fit_tail_norms, "last_block": fit_last_block,
-           "dec2_conv2": fit_dec2_conv, "dec2_block": fit_dec2_block, "dec1_conv2": fit_dec1_conv}[args.train]
+    fit = {stage.choice: globals()["fit_" + stage.name] for stage in STAGES}[args.train]
     history = fit(model, xs, gs, loss=names, steps=args.steps, lr=args.lr, optimizer=args.optimizer,
                   cache_bytes=int(args.cache_gb * 2 ** 30), **opts)
     os.makedirs(op.dirname(op.abspath(args.out)), exist_ok=True)

@@ -779,39 +779,22 @@ class V2ce3d(nn.Module):
         return self._conv(t, None, w2, *bn2, blk.cout, 3, 1, hip.ACT_RELU, residual=res,
                           split=self._split(blk.cout, blk.cout), track=track and pred is None, pred=pred)
 
-    def _block_inputs(self, blk: _ResidualBlock3D, d, x0, x1=None, up_to=None, normed=False):
-        """What ``_block`` hands to conv2, by the launches ``_block`` itself makes in front of it: (relu(bn1(conv1 x)),
-        bn_d(conv_d x)) -- one launch where the shortcut rides on conv1, else the two of the unfused branch.  A block whose
-        shortcut is folded into conv2's K loop has no such pair.  ``normed``: the same launches without activation and with
-        epilogue vectors that leave the two BatchNorms' affine parts out (``_normed_epilogues``): the normalised,
-        pre-affine pair (z1, zd) of ``forward_tail_normed``."""
-        s = blk.stride_hw
-        bn1, down_bn, act = d.get("bn1_eff", d["bn1"]), d["down_bn"], hip.ACT_RELU
-        if normed:
-            bn1, down_bn = self._normed_epilogues(blk, d)
-            act = hip.ACT_NONE
-        if self._fuse_shortcut(blk):
-            return self._conv(x0, x1, d["conv1_w"], *bn1, blk.cout, 3, s, act, up_to=up_to, split=True,
-                              sc=(d["down_w"], *down_bn))
-        assert d.get("fold") is None, "the block's shortcut is folded into conv2: it has no separate residual"
-        t = self._conv(x0, x1, d["conv1_w"], *bn1, blk.cout, 3, s, act, up_to=up_to,
-                       split=self._split(blk.cin, blk.cout))
-        res = self._conv(x0, x1, d["down_w"], *down_bn, blk.cout, 1, s, hip.ACT_NONE, up_to=up_to,
-                         split=self._split(blk.cin, blk.cout, 1, s))
-        return t, res
-
-    def _block_inputs_unfused(self, blk: _ResidualBlock3D, d, x0, x1=None, up_to=None, normed=False):
-        """(relu(bn1(conv1 x)), bn_d(conv_d x)) of a block whose shortcut normally rides in conv2's K loop (``_fold_shortcut``)
-        or has a launch of its own: conv1 as ``_block`` launches it in front of such a conv2, and the shortcut's own 1x1x1
-        launch of ``_block``'s last branch (``down_w`` and ``down_bn`` are prepared for every block).  ``normed``: the same
-        launches without activation and with epilogue vectors that leave the two BatchNorms' affine parts out
-        (``_normed_epilogues``): the normalised, pre-affine pair (z1, zd) of ``forward_dec2_normed``."""
-        assert not self._fuse_shortcut(blk), "the block's shortcut rides on conv1's launch: _block_inputs returns its pair"
+    def _block_inputs(self, blk: _ResidualBlock3D, d, x0, x1=None, up_to=None, normed=False, unfold=False):
+        """What conv2 of the block reads, (relu(bn1(conv1 x)), bn_d(conv_d x)), by ``_block``'s own launches in front of it:
+        one launch where the shortcut rides on conv1 (``_fuse_shortcut``); else conv1 as ``_block`` launches it -- in two
+        parts where the block has ``conv1_skip_w`` -- and the shortcut's own 1x1x1 launch of ``_block``'s last branch
+        (``down_w`` and ``down_bn`` are prepared for every block).  A block whose shortcut is folded into conv2's K loop
+        (``_fold_shortcut``) has no such pair in the model's own forward: ``unfold`` makes it by these launches, and without
+        it such a block is refused.  ``normed``: the same launches without activation and with epilogue vectors that leave
+        the two BatchNorms' affine parts out (``_normed_epilogues``): the normalised, pre-affine pair (z1, zd)."""
         s = blk.stride_hw
         w1, bn1, down_bn, act = d["conv1_w"], d.get("bn1_eff", d["bn1"]), d["down_bn"], hip.ACT_RELU
         if normed:
             bn1, down_bn = self._normed_epilogues(blk, d)
             act = hip.ACT_NONE
+        if self._fuse_shortcut(blk):
+            return self._conv(x0, x1, w1, *bn1, blk.cout, 3, s, act, up_to=up_to, split=True, sc=(d["down_w"], *down_bn))
+        assert unfold or d.get("fold") is None, "the block's shortcut is folded into conv2: it has no separate residual"
         if d.get("conv1_skip_w") is not None and x1 is not None and self._up2_ok(x0, x1, w1, up_to):
             part = self._conv_up_part(x0, x1, w1, *bn1, blk.cout, up_to)
             t = self._conv(x1, None, d["conv1_skip_w"], bn1[0], d["zero_shift"], blk.cout, 3, 1, act, residual=part,
@@ -923,10 +906,7 @@ class V2ce3d(nn.Module):
         the logical width in ``.lw``, without gradient (last_conv.py: ``LastConv`` turns them into ``forward_features``'s
         tensor).  The trunk runs exactly as in ``forward_features`` -- the same spectral-norm power iteration (one per
         call, conv2's included), range-guard policy and precision -- and stops in front of conv2."""
-        t, res = self._guarded_forward(x, False, features="tail")
-        if hasattr(t, "absmax"):        # the range slot is a view of a table the next call clears: keep this call's value
-            t.absmax = t.absmax.clone()
-        return t, res
+        return self._stop_at(x, "tail")
 
     @torch.no_grad()
     def forward_tail_normed(self, x: torch.Tensor):
@@ -937,7 +917,7 @@ class V2ce3d(nn.Module):
         bn_d.weight zd + bn_d.bias).  The trunk runs exactly as in ``forward_tail_inputs`` -- the same launches, power
         iteration (one per call), range-guard policy and precision; only the epilogue vectors and the activation of
         the block's first launches differ."""
-        return self._guarded_forward(x, False, features="normed")
+        return self._stop_at(x, "normed")
 
     @torch.no_grad()
     def forward_tail_sources(self, x: torch.Tensor):
@@ -947,11 +927,7 @@ class V2ce3d(nn.Module):
         gradient (last_block.py: ``TailConvs`` turns them into ``forward_tail_normed``'s pair).  The trunk runs exactly as
         in ``forward_tail_inputs`` -- the same spectral-norm power iteration (one per call, the last block's included),
         range-guard policy and precision -- and stops in front of the last decoder block."""
-        x0, x1 = self._guarded_forward(x, False, features="sources")
-        for a in (x0, x1):              # the range slots are views of a table the next call clears: keep this call's values
-            if hasattr(a, "absmax"):
-                a.absmax = a.absmax.clone()
-        return x0, x1
+        return self._stop_at(x, "sources")
 
     @torch.no_grad()
     def forward_dec2_inputs(self, x: torch.Tensor):
@@ -963,11 +939,7 @@ class V2ce3d(nn.Module):
         normally rides in conv2's K loop and res2 never exists: this accessor makes conv1's launch and the shortcut's own
         1x1x1 launch instead.  Everything in front of the block runs exactly as in ``forward_tail_sources`` -- the same
         spectral-norm power iteration (one per call, every layer's included), range-guard policy and precision."""
-        out = self._guarded_forward(x, False, features="dec2")
-        for a in out:                   # the range slots are views of a table the next call clears: keep this call's values
-            if hasattr(a, "absmax"):
-                a.absmax = a.absmax.clone()
-        return out
+        return self._stop_at(x, "dec2")
 
     @torch.no_grad()
     def forward_dec1_inputs(self, x: torch.Tensor):
@@ -982,11 +954,7 @@ class V2ce3d(nn.Module):
         iteration (one per call, every layer's included), range-guard policy and precision."""
         if len(self.UNet.decoders) < 3:
             raise ValueError("the model has fewer than 3 decoders")
-        out = self._guarded_forward(x, False, features="dec1")
-        for a in out:                   # the range slots are views of a table the next call clears: keep this call's values
-            if hasattr(a, "absmax"):
-                a.absmax = a.absmax.clone()
-        return out
+        return self._stop_at(x, "dec1")
 
     @torch.no_grad()
     def forward_dec2_sources(self, x: torch.Tensor):
@@ -997,11 +965,7 @@ class V2ce3d(nn.Module):
         without gradient (dec2_block.py: ``Dec2Convs`` turns the first two into ``forward_dec2_normed``'s pair).  Everything
         in front of the block runs exactly as in ``forward_dec2_inputs`` -- the same spectral-norm power iteration (one per
         call, every layer's included), range-guard policy and precision -- and stops in front of the block."""
-        out = self._guarded_forward(x, False, features="dec2_sources")
-        for a in out:                   # the range slots are views of a table the next call clears: keep this call's values
-            if hasattr(a, "absmax"):
-                a.absmax = a.absmax.clone()
-        return out
+        return self._stop_at(x, "dec2_sources")
 
     @torch.no_grad()
     def forward_dec2_normed(self, x: torch.Tensor):
@@ -1012,7 +976,19 @@ class V2ce3d(nn.Module):
         into ``forward_dec2_inputs``'s: t2 = relu(bn1.weight z1 + bn1.bias), res2 = bn_d.weight zd + bn_d.bias).  The trunk
         runs exactly as in ``forward_dec2_inputs`` -- the same launches, power iteration (one per call), range-guard policy
         and precision; only the epilogue vectors and the activation of the block's first launches differ."""
-        out = self._guarded_forward(x, False, features="dec2_normed")
+        return self._stop_at(x, "dec2_normed")
+
+    # where an accessor stops the trunk: name -> (the decoder, counted from the end; what is returned there: "sources", the
+    # two tensors the block reads, "inputs", the two its conv2 launch reads, or "normed", those two in front of the
+    # BatchNorms' affine parts and the relu)
+    STOPS = {"tail": (1, "inputs"), "normed": (1, "normed"), "sources": (1, "sources"),
+             "dec2": (2, "inputs"), "dec2_normed": (2, "normed"), "dec2_sources": (2, "sources"),
+             "dec1": (3, "inputs")}
+
+    def _stop_at(self, x, stop):
+        """The trunk up to ``STOPS[stop]``.  The range slots (``.absmax``) of the returned tensors are views of a table the
+        next call clears: every one is cloned, so each tensor keeps this call's value."""
+        out = self._guarded_forward(x, False, features=stop)
         for a in out:
             if hasattr(a, "absmax"):
                 a.absmax = a.absmax.clone()
@@ -1045,15 +1021,11 @@ class V2ce3d(nn.Module):
                 return self._forward(x, return_intermediates, features=features)
 
     def _forward(self, x, return_intermediates, features=False):
-        """features=True: stop in front of UNet.pred and return its input (forward_features); features="tail": stop in front
-        of the last decoder block's conv2 and return its two inputs (forward_tail_inputs); features="normed": the same two launches
-        without the BatchNorms' affine parts and the relu (forward_tail_normed); features="sources": stop in front of the last decoder
-        block and return the two tensors it reads (forward_tail_sources); features="dec2": stop in front of conv2 of the decoder before
-        it and return that launch's two inputs and the last block's skip tensor (forward_dec2_inputs); features="dec2_normed": the same
-        launches without the BatchNorms' affine parts and the relu (forward_dec2_normed); features="dec2_sources": stop in front of
-        that decoder and return the two tensors it reads and the last block's skip tensor (forward_dec2_sources); features="dec1": stop
-        in front of conv2 of UNet.decoders[1] and return that launch's two inputs and the skip tensors of the two blocks behind it
-        (forward_dec1_inputs); the default launches are today's."""
+        """features=True: stop in front of UNet.pred and return its input (forward_features).  features=a key of ``STOPS``, which
+        names a decoder counted from the end and a kind: stop at that decoder and return a tuple -- its two sources (h, skip), or
+        what ``_block_inputs`` makes of them (the two inputs of its conv2 launch, or the normalised pair in front of them) --
+        followed by the skip tensors of the decoders behind it, which the layers that replay those decoders read.  The default
+        launches are those of the plain forward."""
         if self._prep is None:
             self._prepare()
         P, U = self._prep, self.UNet
@@ -1086,36 +1058,20 @@ class V2ce3d(nn.Module):
             h = self._block(blk, P[f"res{i}"], h)
             inter[f"res{i}"] = self.to_planar(h) if return_intermediates else None
         fuse = P["pred_fused"] if not (return_intermediates or features) else None
+        back, kind = self.STOPS.get(features, (0, None)) if isinstance(features, str) else (0, None)
+        stop_at = len(U.decoders) - back if back else -1
         for i, (blk, skip) in enumerate(zip(U.decoders, reversed(skips))):       # :357-365
             last = i == len(U.decoders) - 1
-            if features == "dec1" and i == len(U.decoders) - 3:
-                later = list(reversed(skips))[i + 1:i + 3]
-                h = self._block_inputs_unfused(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4]))) + \
-                    tuple(later)
-                break
-            if features == "dec2" and i == len(U.decoders) - 2:
-                nxt = list(reversed(skips))[i + 1]
-                h = self._block_inputs_unfused(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4]))) + (nxt,)
-                break
-            if features == "dec2_normed" and i == len(U.decoders) - 2:
-                nxt = list(reversed(skips))[i + 1]
-                h = self._block_inputs_unfused(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])),
-                                               normed=True) + (nxt,)
-                break
-            if features == "dec2_sources" and i == len(U.decoders) - 2:
-                h = (h, skip, list(reversed(skips))[i + 1])
-                break
-            if last and features == "sources":
-                h = (h, skip)
-                break
-            if last and features in ("tail", "normed"):
-                h = self._block_inputs(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])),
-                                       normed=features == "normed")
+            if i == stop_at:
+                h = (h, skip) if kind == "sources" else \
+                    self._block_inputs(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])),
+                                       normed=kind == "normed", unfold=back > 1)
+                h += tuple(reversed(skips))[i + 1:]
                 break
             h = self._block(blk, P[f"dec{i}"], h, skip, up_to=(skip.shape[3], getattr(skip, "lw", skip.shape[4])),
                             pred=fuse if last else None)
             inter[f"dec{i}"] = self.to_planar(h) if return_intermediates else None
-        if features in ("tail", "normed", "sources", "dec2", "dec2_normed", "dec2_sources", "dec1"):
+        if back:
             out = tuple(a if getattr(a, "c16", False) else self.to_c16(a) for a in h)
         elif features:
             # (the exact-f32 kernels produce planar tensors: one copy into the layout the head kernels take)
