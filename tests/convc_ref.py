@@ -13,6 +13,10 @@ WALK_PAIR = (128, 128)
 # WIDE run three shapes only; 512 catches anything sized for four groups
 WIDE = ((256, 256), (512, 512), (512, 32), (32, 512))
 WIDE_SHAPES = ((2, 3, 5, 7), (1, 2, 3, 70), (1, 3, 20, 70))
+# the widest pairs on the walk shape (396 tiles).  (256, 256) has 64 pairs: the default grid is 4 shares of 99 tiles, three
+# flushes of the f32 chain and three tiles more, and the prime grid (97 // 64) one share; (512, 512) has 256 pairs: one share
+# of 396 tiles and twelve flushes by default, on the largest workspace there is
+LONG_WALKS = ((256, 256, WALK, 0), (256, 256, WALK, None), (512, 512, WALK, 0))
 # where the older entries give the same bytes
 NARROW = ((32, 32), (64, 64), (64, 32), (32, 64))
 NARROW_SHAPES = ((1, 3, 20, 70), WALK)
@@ -26,7 +30,7 @@ def runs():
     out = [(ci, co, shape, mult) for ci, co in PAIRS for shape, mult in SMALL.items()]
     out += [(*WALK_PAIR, WALK, 0), (*WALK_PAIR, WALK, None)]
     out += [(ci, co, shape, SMALL[shape]) for ci, co in WIDE for shape in WIDE_SHAPES]
-    return out
+    return out + list(LONG_WALKS)
 
 
 def run_id(run):

@@ -1,4 +1,4 @@
-"""What the probe tests of the eight gradient kernels share (tests/test_grad_probe_cpu.py, tests/test_gpu_grad_probes.py): the
+"""What the probe tests of the eleven gradient kernels share (tests/test_grad_probe_cpu.py, tests/test_gpu_grad_probes.py): the
 case table, the data builders of the four probes, the share arithmetic of the weight-gradient grids, the three assertions of
 the absorption probe and a numpy model of one output element of a hypothetical weight-gradient kernel.  No GPU.
 
@@ -10,20 +10,25 @@ rounded there.  A case is (kind, channels):
   dgrad    (cin, cout)       v2ce_conv32_dgrad at (32, 32), v2ce_convn_dgrad at convn_ref.PAIRS      weight, y, upstream
   updgrad  (64, 32, 32)      v2ce_convup_dgrad                                                      weight, short, g1, gd
   head     (cout,)           v2ce_pred_head_grads at grad_walk_ref.HEAD_COUTS                       feat, y, upstream, weight
+  wgrad    (cin, cout)       v2ce_convc_wgrad at WIDE_PAIRS = (128, 128), (512, 32), (32, 512), (512, 512)   x, y, upstream
+  dgrad    (cin, cout)       v2ce_convc_dgrad at WIDE_PAIRS                                         weight, y, upstream
+  updgrad  (c0, c1, cout)    v2ce_convupn_dgrad at convupn_ref.TRIPLES                              weight, short, g1, gd
 
-with the inputs in the reference's layouts as f32 tensors on the CPU under the names on the right.  In every kind one operand
-is a gradient coming from behind (role "up": upstream, g1, gd) and the other one is what it is multiplied with (role "other").
+(the last three rows are appended to CASES behind the others, whose indices seed their data: `is_new`) with the inputs in
+the reference's layouts as f32 tensors on the CPU under the names on the right.  In every kind one operand is a gradient coming from behind (role "up": upstream, g1, gd) and the other one is what it is multiplied with (role "other").
 
 Probe 1, wide integers.  Sparse upstream gradients, dense other operands, every value an odd integer of 12 significant bits
 (2049 .. 2895, either sign), so a product is an odd integer of 23 significant bits below 2^23 and an element's two terms sum
 below 2^24: every f32 order of every sum is exact, while a product formed at less than f32 precision is not.  The one element
 that collects more is d_x0 of v2ce_convup_dgrad (the 2 x 2 pool: up to four terms): the weights of its 64 channels are odd
-integers of 11 bits (1025 .. 1447), products of 22 bits.
+integers of 11 bits (1025 .. 1447), products of 22 bits.  The appended cases need up to 512 positions, or 256 with disjoint
+3 x 3 x 3 neighbourhoods: they have a shape, [2, 4, 5, 131], and slot tables of their own (p1w_slots).
 
 Probe 2, absorption.  Ones everywhere and one anchor of 2^24, 2^32 or 2^36: what an f32 chain, an f32 partial slot or an f32
 finish loses next to the anchor is an integer that the header's sentences bound.
 
-Probe 3, power-of-two scale equivariance: per-channel exponents for the normal data of the walks.
+Probe 3, power-of-two scale equivariance: per-channel exponents for the normal data of the walks (the appended cases:
+[1, 3, 20, 70], 60 tiles with a ragged second tile column).
 
 Probe 4, the underflow term: the same normal data scaled so that products lie at the lower end of f32's normal range."""
 import numpy as np
@@ -36,12 +41,23 @@ from tests.last_conv_ref import ulp32
 
 CASES = [("wgrad", (32, 32))] + [("wgrad", p) for p in R.PAIRS] + [("upwgrad", RU.OLD)] + [("upwgrad", t) for t in RU.TRIPLES] + \
         [("dgrad", (32, 32))] + [("dgrad", p) for p in R.PAIRS] + [("updgrad", RU.OLD)] + [("head", (c,)) for c in G.HEAD_COUTS]
+# appended, never inserted: a case's index seeds its data.  (128, 128) is the model's layer and the first width at which the
+# input gradient fetches its weights again per tile, the asymmetric pairs catch a transposed or truncated group index,
+# 512 -> 512 is 256 pairs: a default grid of one share
+N_OLD = len(CASES)
+WIDE_PAIRS = ((128, 128), (512, 32), (32, 512), (512, 512))
+CASES += [("wgrad", p) for p in WIDE_PAIRS] + [("dgrad", p) for p in WIDE_PAIRS] + [("updgrad", t) for t in RU.TRIPLES]
 WGRAD_CASES = [c for c in CASES if c[0] in ("wgrad", "upwgrad")]
 CONV_CASES = [c for c in CASES if c[0] != "head"]
 
 
 def case_id(case):
     return case[0] + "_" + "_".join(map(str, case[1]))
+
+
+def is_new(case):
+    """The appended cases: v2ce_convc_wgrad, v2ce_convc_dgrad and v2ce_convupn_dgrad."""
+    return CASES.index(case) >= N_OLD
 
 
 OUTPUTS = {"wgrad": ("weight", "shift"), "upwgrad": ("weight", "short", "short_bias"), "dgrad": ("x", "res"),
@@ -54,8 +70,20 @@ ROLES = {"wgrad": {"up": ("upstream",), "other": ("x",)}, "upwgrad": {"up": ("g1
          "head": {"up": ("upstream",), "other": ("feat", "weight")}}
 
 
-def truth(kind, z):
-    """The f64 truth of a case's outputs on the device of its inputs, under the kernel's output names."""
+def updgrad_truth(c0, weight, short, g1, gd):
+    """grad_walk_ref.convup_dgrad at any channel counts, c0 of the input channels upsampled: the per-tap f64 matmuls, the
+    shortcut's matmul and the 2 x 2 pool (tests/test_grad_probe_cpu.py holds it to convupn_dgrad_ref.dgrad)."""
+    g, s = G.f64(g1), G.f64(gd)
+    w = G.f64(short).to(g.device).reshape(short.shape[0], -1)
+    d, a = G._tap_transposed(weight, g)
+    dX, aX = d + G.unrows(w.t() @ G.rows(s), s), a + G.unrows(w.abs().t() @ G.rows(s).abs(), s)
+    return {"d_x0": G.pooled(dX[:, :c0]), "d_x1": dX[:, c0:].contiguous(), "abs_x0": G.pooled(aX[:, :c0]),
+            "abs_x1": aX[:, c0:].contiguous()}
+
+
+def truth(kind, z, ch=None):
+    """The f64 truth of a case's outputs on the device of its inputs, under the kernel's output names.  ch: the channel
+    triple of an updgrad case other than (64, 32, 32), which the tensors alone do not tell."""
     if kind == "wgrad":
         t = G.conv32_wgrad(z["x"], z.get("y"), z["upstream"])
         return {"weight": t["d_weight"], "shift": t["d_shift"]}
@@ -66,18 +94,19 @@ def truth(kind, z):
         t = G.conv32_dgrad(z["weight"], z.get("y"), z["upstream"])
         return {"x": t["d_x"], "res": t["d_res"]}
     if kind == "updgrad":
-        t = G.convup_dgrad(z["weight"], z["short"], z["g1"], z["gd"])
+        t = G.convup_dgrad(z["weight"], z["short"], z["g1"], z["gd"]) if ch in (None, RU.OLD) else \
+            updgrad_truth(ch[0], z["weight"], z["short"], z["g1"], z["gd"])
         return {"x0": t["d_x0"], "x1": t["d_x1"]}
     t = G.pred_head_grads(z["feat"], z.get("y"), z["upstream"], z["weight"])
     return {"weight": t["d_weight"], "bias": t["d_bias"], "feat": t["d_feat"]}
 
 
-def abs_truth(kind, z):
+def abs_truth(kind, z, ch=None):
     """An element's sum of |terms|: the truth of the absolute values, the mask applied first."""
     a = {k: v.abs() for k, v in z.items() if k != "y" and v is not None}
     if z.get("y") is not None:
         a["upstream"] = G.masked(z["y"], z["upstream"]).abs()
-    return truth(kind, a)
+    return truth(kind, a, ch)
 
 
 def n_terms_updgrad(shape):
@@ -163,7 +192,7 @@ def p1_dense(gen, shape, late):
     return torch.where(late, odd_integers(gen, shape, (mid, WIDE[1])), odd_integers(gen, shape, (WIDE[0], mid)))
 
 
-def p1_sparse(gen, channels, positions, per_pos):
+def p1_sparse(gen, channels, positions, per_pos, shape=P1_SHAPE):
     """[B, channels, L, H, W] of zeros with `per_pos` odd integers at each position: slot s = k per_pos + j of position k is
     channel s mod channels, so len(positions) per_pos / channels positions feed every channel.  The two terms of an element
     come from slots j = 0 and j = 1 of one position (input gradients, the head's d_feat) or from positions k and
@@ -171,7 +200,7 @@ def p1_sparse(gen, channels, positions, per_pos):
     operand's classes (p1_dense) follow the same order -- columns near the second half's positions and odd output channels
     hold the larger class -- so of an element's two terms the second has the larger |up|, the larger |other| and the larger
     |up| + |other|: neither the rounding errors of an 11-bit operand nor the dropped low bits of the two terms can cancel."""
-    B, L, H, W = P1_SHAPE
+    B, L, H, W = shape
     assert (len(positions) * per_pos) % channels == 0 and per_pos in (1, 2)
     out = torch.zeros((B, channels, L, H, W), dtype=torch.float32)
     q = (WIDE[1] - WIDE[0]) // 4
@@ -193,6 +222,8 @@ def p1_inputs(case):
     element of d_weight and d_short a sum of two products (one where a tap leaves the tensor).  Input gradients: cout / 2
     positions x 2 channels, every d_x element a sum of two products or zero.  v2ce_convup_dgrad: g1 at 32 positions and gd at
     32 others, one channel each: a d_x1 element is one product, a d_x0 element up to four.  Head: cout positions x 2."""
+    if is_new(case):
+        return p1w_inputs(case)
     kind, ch = case
     B, L, H, W = P1_SHAPE
     gen = torch.Generator().manual_seed(P1_SEED + 31 * CASES.index(case))
@@ -223,6 +254,74 @@ def p1_inputs(case):
     up = p1_sparse(gen, cout, p1_pick(cout), 2)
     return {"feat": p1_dense(gen, act(G.C), cols), "upstream": up, "y": p1_y(gen, up).abs(),
             "weight": p1_dense(gen, (cout, G.C), odd_co(cout, 1))}
+
+
+# the appended cases: up to 512 positions
+
+P1W_SHAPE = (2, 4, 5, 131)                    # 72 tiles: three tile rows (the last of one row), three tile columns (the last of 3)
+P1W_STEP = {"wgrad": 3, "dgrad": 3, "updgrad": 4}
+
+
+def p1_shape(case):
+    return P1W_SHAPE if is_new(case) else P1_SHAPE
+
+
+def p1w_slots(kind):
+    """The positions (b, l, h, w) of P1W_SHAPE that a sparse gradient of the appended cases may use, column by column.
+    dgrad: frames 0 and 3, rows 0 and 3, every third column -- 352 positions whose 3 x 3 x 3 neighbourhoods are disjoint,
+    so that no input-gradient element reaches two.  updgrad: every fourth column of the same frames and rows -- 264
+    positions of which no 2 x 2 pool of output positions (rows 2 h0 - 1 .. 2 h0 + 2 and as many columns of a neighbourhood)
+    reaches two.  wgrad, whose elements sum over the positions whatever they are: every frame and every row of every third
+    column, 1760 positions.  Slot 0 is (0, 0, 0, 0), the first position of the first tile and a corner of the first frame;
+    the last one lies in the three-column last tile of the last frame (wgrad: in its one-row last tile row)."""
+    B, L, H, W = P1W_SHAPE
+    frames, lines = (range(L), range(H)) if kind == "wgrad" else ((0, 3), (0, 3))
+    return [(b, l, h, w) for w in range(0, W, P1W_STEP[kind]) for b in range(B) for l in frames for h in lines]
+
+
+def p1w_pick(kind, n):
+    """n of the slots: the first n / 2 and the last n / 2, so that the two halves share no column and a column within a tap
+    of the one half is within a tap of no position of the other -> (positions, the first column of the later half)."""
+    slots = p1w_slots(kind)
+    first, second = slots[:n // 2], slots[len(slots) - n // 2:]
+    assert n % 2 == 0 and n <= len(slots) and first[-1][3] + 3 <= second[0][3]
+    return first + second, second[0][3]
+
+
+def p1w_inputs(case):
+    """The inputs of probe 1 of an appended case at P1W_SHAPE, in the scheme of p1_inputs.  wgrad: cout positions x 2
+    channels, the two terms of an element at positions k and k + cout / 2, x of the larger class in the columns from one
+    before the later half's first.  dgrad: cout / 2 positions x 2 channels, every output channel once, the odd ones with
+    the larger gradients and the larger weights.  updgrad: g1 at cout positions and gd at cout others, one channel each: a
+    d_x1 element is one product, a d_x0 element up to four products of one gradient value with four taps of one (co, ci).
+    The weights of the c0 upsampled channels are 11-bit integers 4 m + 1 (1025 .. 1445) whose sign depends on (co, ci)
+    alone: the four terms have one sign, and what an operand loses at 11 bits (the gradient), at 10 bits (these weights:
+    every one of them rounds towards zero by one) or with its lowest bit has one sign in all four, so it cannot cancel."""
+    kind, ch = case
+    B, L, H, W = P1W_SHAPE
+    gen = torch.Generator().manual_seed(P1_SEED + 31 * CASES.index(case))
+    if kind == "wgrad":
+        cin, cout = ch
+        at, later = p1w_pick(kind, cout)
+        up = p1_sparse(gen, cout, at, 2, P1W_SHAPE)
+        late = (torch.arange(W) >= later - 1).view(1, 1, 1, 1, W)
+        return {"x": p1_dense(gen, (B, cin, L, H, W), late), "upstream": up, "y": p1_y(gen, up)}
+    if kind == "dgrad":
+        cin, cout = ch
+        up = p1_sparse(gen, cout, p1w_pick(kind, cout // 2)[0], 2, P1W_SHAPE)
+        odd_co = (torch.arange(cout) % 2 == 1).view(cout, 1, 1, 1, 1)
+        return {"weight": p1_dense(gen, (cout, cin, 3, 3, 3), odd_co), "upstream": up, "y": p1_y(gen, up)}
+    assert kind == "updgrad"
+    c0, c1, cout = ch
+    at = p1w_pick(kind, 2 * cout)[0]
+    mine = [sum(p) % 2 == 0 for p in at]        # a checkerboard (the columns are even): either gets every batch element, frame and row
+    w = odd_integers(gen, (cout, c0 + c1, 3, 3, 3))
+    sign = torch.randint(0, 2, (cout, c0, 1, 1, 1), generator=gen) * 2 - 1
+    quarter = torch.randint(POOLED[0] // 4, POOLED[1] // 4, (cout, c0, 3, 3, 3), generator=gen)
+    w[:, :c0] = (sign * (quarter * 4 + 1)).to(torch.float32)
+    return {"weight": w, "short": odd_integers(gen, (cout, c0 + c1)),
+            "g1": p1_sparse(gen, cout, [p for p, m in zip(at, mine) if m], 1, P1W_SHAPE),
+            "gd": p1_sparse(gen, cout, [p for p, m in zip(at, mine) if not m], 1, P1W_SHAPE)}
 
 
 def round_to_bits(t, bits):
@@ -332,6 +431,8 @@ def boundaries(sizes, tile=G.TILE_H * G.TILE_W):
 # probes 3 and 4: the normal data of the walks
 
 P3_SHAPE = R.WALK                             # [2, 3, 43, 131]: 396 ragged tiles
+P3W_SHAPE = (1, 3, 20, 70)                    # the appended cases: 60 tiles, a ragged second tile column (a per-element property
+                                              # needs no long walk); one share of a weight gradient flushes mid-walk
 P3_SEED = 709                                 # (707 and 708 draw an exact 0.0, which no exponent scales)
 P3_MAX_EXP = 16
 P3_RANGE = (2.0 ** -60, 2.0 ** 40)
@@ -339,9 +440,27 @@ P4_SHAPE = (1, 2, 5, 70)
 P4_SEED = 808
 
 
+def p3_shape(case):
+    return P3W_SHAPE if is_new(case) else P3_SHAPE
+
+
 def normal_inputs(case, shape, seed):
-    """The suite's seeded standard normals of a case at `shape` under this file's names."""
+    """The suite's seeded standard normals of a case at `shape` under this file's names.  The appended cases draw up to
+    7e6 weights, among which an exact 0.0 is likely (f32 normals hold one in about 2^-24 draws): there a 0.0 of a value
+    tensor becomes 1.0, so that every value has an exponent to scale."""
+    z = _normal_inputs(case, shape, seed)
+    if is_new(case):
+        z = {k: (v if k == "y" else torch.where(v == 0, torch.ones_like(v), v)) for k, v in z.items()}
+    return z
+
+
+def _normal_inputs(case, shape, seed):
     kind, ch = case
+    if kind == "updgrad" and ch != RU.OLD:                              # (convupn_ref.inputs has the gradients, no weights)
+        z = RU.inputs(shape, *ch, False, seed)
+        gen = torch.Generator().manual_seed(seed + 31 * CASES.index(case))
+        return {"weight": G.normals(gen, (ch[2], ch[0] + ch[1], 3, 3, 3)), "short": G.normals(gen, (ch[2], ch[0] + ch[1])),
+                "g1": z["g1"], "gd": z["gd"]}
     if kind == "head":
         z = G.head_inputs(shape, False, seed, ch[0])
         return {"feat": z["feat"], "y": z["y_head"], "upstream": z["up_head"], "weight": z["w_head"]}

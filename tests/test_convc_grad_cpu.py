@@ -151,13 +151,19 @@ def test_integer_sums_of_check_a_are_exact_in_f32():
 
 def test_run_lists():
     runs = R.runs()
-    assert len(runs) == len(set(runs)) == 4 * 6 + 2 + 4 * 3
+    assert len(runs) == len(set(runs)) == 4 * 6 + 2 + 4 * 3 + 3
     assert {(ci, co) for ci, co, _, _ in runs} == set(R.PAIRS + R.WIDE)
     assert all(ci in R.CHANNELS and co in R.CHANNELS for ci, co in R.PAIRS + R.WIDE + R.NARROW)
     assert all(max(ci, co) > 64 for ci, co in R.PAIRS + R.WIDE) and all(max(ci, co) <= 64 for ci, co in R.NARROW)
     assert len({R.run_id(r) for r in runs}) == len(runs)
-    wide = [r for r in runs if (r[0], r[1]) in R.WIDE]
+    wide = [r for r in runs if (r[0], r[1]) in R.WIDE and r not in R.LONG_WALKS]
     assert {r[2] for r in wide} == set(R.WIDE_SHAPES)
+    # the long walks of the widest pairs: shares of more than one chain at the default grid, up to twelve flushes
+    tiles, chain = G.conv_tiles(*R.WALK), hip.WGRAD_CHAIN // 128
+    assert runs[-3:] == list(R.LONG_WALKS) and tiles == 396 and chain == 32
+    shares = [R.wgrad_shares(ci, co, tiles, R.cap_of(ci, co, m)) for ci, co, _, m in R.LONG_WALKS]
+    assert shares == [4, 1, 1] and divmod(tiles // 4, chain) == (3, 3) and divmod(tiles, chain) == (12, 12)
+    assert int(np.prod(R.WALK)) * G.INT_MAX ** 2 == 304182             # the largest integer sum of check A
     assert all(R.cap_of(ci, co, m) == R.pairs_of(ci, co) for ci, co, s, m in wide if s == (1, 3, 20, 70))
 
 

@@ -7,7 +7,9 @@ convn_ref.SMALL ([1,3,20,70] with max_workgroups = the pair count: one share of 
 and a partial chain behind it); (128, 128) also runs the walk shape [2,3,43,131] (396 tiles, uneven shares) at the default
 grid and at max_workgroups = 97.  convc_ref.WIDE = (256, 256), (512, 512), (512, 32), (32, 512) run [2,3,5,7], [1,2,3,70]
 and [1,3,20,70] (one share).  The asymmetric pairs catch a transposed or truncated group index, 512 anything sized for four
-groups.
+groups.  convc_ref.LONG_WALKS: (256, 256) on the walk shape at the default grid (64 pairs, 4 shares of 99 tiles: three flushes
+of the f32 chain and three tiles more) and at max_workgroups = 97 (one share), (512, 512) at the default grid (256 pairs, one
+share of 396 tiles, twelve flushes, the largest workspace).
 
 Check A, exact.  Integers 1 .. 3 in every value tensor, a normal y with signed zeros for the mask, outputs pre-filled with
 NaN.  Every sum is an integer below 2^24, so every element must equal the f64 truth bit for bit; the padding columns of d_x

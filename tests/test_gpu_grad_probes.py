@@ -1,9 +1,17 @@
-"""The precision contracts of the eight gradient kernels on data that can see them fail: v2ce_conv32_wgrad,
-v2ce_convup_wgrad, v2ce_convn_wgrad, v2ce_convupn_wgrad, v2ce_conv32_dgrad, v2ce_convup_dgrad, v2ce_convn_dgrad and
-v2ce_pred_head_grads through their checked Python entries, against the f64 truths of the suite computed on the device
+"""The precision contracts of the eleven gradient kernels on data that can see them fail: v2ce_conv32_wgrad,
+v2ce_convup_wgrad, v2ce_convn_wgrad, v2ce_convupn_wgrad, v2ce_conv32_dgrad, v2ce_convup_dgrad, v2ce_convn_dgrad,
+v2ce_pred_head_grads, v2ce_convc_wgrad, v2ce_convc_dgrad and v2ce_convupn_dgrad through their checked Python entries,
+against the f64 truths of the suite computed on the device
 (tests/grad_probe_ref.py builds the data and states the assertions; tests/test_grad_probe_cpu.py proves the data's conditions
 and shows on a numpy model which assertion catches which fault).  The N-channel kernels run at convn_ref.PAIRS and
 convupn_ref.TRIPLES.  The integers 1 .. 3 and the standard normals of the other tests cannot see these sentences fail.
+
+The last three entries are the cases appended to grad_probe_ref.CASES:
+  wgrad    (128, 128), (512, 32), (32, 512), (512, 512)     conv_grads.convc_wgrad (up to 256 pairs: one share by default)
+  dgrad    (128, 128), (512, 32), (32, 512), (512, 512)     conv_grads.convc_dgrad (the instance that fetches weights per tile)
+  updgrad  (128, 64, 64), (64, 64, 32), (128, 32, 64)       dec2_block.convupn_dgrad
+with shapes of their own in probes 1 and 3: [2, 4, 5, 131] (up to 512 sparse positions, 256 with disjoint neighbourhoods;
+the input gradients also at max_workgroups = 97) and [1, 3, 20, 70] (60 tiles, a ragged second tile column).
 
 Probe 1, "exact f32 products".  [2, 3, 5, 131], sparse upstream gradients and dense operands of odd 12-bit integers: every
 product has 22 or 23 significant bits, every element's sum of |terms| is below 2^24, so every output must equal the f64
@@ -36,7 +44,8 @@ from tests import grad_probe_ref as P
 from tests import grad_walk_ref as G
 from tests import last_block_dgrad_ref as BD
 from tests.last_conv_ref import ulp32
-from v2ce_toolbox_amd import dec2_block, dec2_conv, hip, last_block, last_conv, pred_head
+from tests import convupn_ref as RU
+from v2ce_toolbox_amd import conv_grads, dec2_block, dec2_conv, hip, last_block, last_conv, pred_head
 
 pytestmark = pytest.mark.gpu
 
@@ -60,7 +69,7 @@ def run(case, z, shape, cap=0):
     kw = {"max_workgroups": cap}
     if kind == "wgrad":
         cin, cout = ch
-        f = last_conv.conv32_wgrad if ch == (32, 32) else dec2_conv.convn_wgrad
+        f = last_conv.conv32_wgrad if ch == (32, 32) else conv_grads.convc_wgrad if P.is_new(case) else dec2_conv.convn_wgrad
         g = f(c16(z["x"]), None if z["y"] is None else c16(z["y"]), c16(z["upstream"]),
               out={"weight": nan((cout, cin, 3, 3, 3)), "shift": nan((cout,))}, **kw)
     elif kind == "upwgrad":
@@ -70,7 +79,7 @@ def run(case, z, shape, cap=0):
               out={"weight": nan((cout, c0 + c1, 3, 3, 3)), "short": nan((cout, c0 + c1)), "short_bias": nan((cout,))}, **kw)
     elif kind == "dgrad":
         cin, cout = ch
-        f = last_conv.conv32_dgrad if ch == (32, 32) else dec2_conv.convn_dgrad
+        f = last_conv.conv32_dgrad if ch == (32, 32) else conv_grads.convc_dgrad if P.is_new(case) else dec2_conv.convn_dgrad
         up = c16(z["upstream"])
         out = {"x": nan((B, L, cin // 16, H, up.shape[4], 16)), "res": nan(up.shape)}
         for t in out.values():
@@ -79,8 +88,9 @@ def run(case, z, shape, cap=0):
     elif kind == "updgrad":
         g1 = c16(z["g1"])
         x0 = nan((B, L, ch[0] // 16, (H + 1) // 2, G.pitch_of((W + 1) // 2), 16))
-        g = last_block.convup_dgrad(z["weight"].to(DEV), z["short"].to(DEV), g1, c16(z["gd"]),
-                                    out={"x0": x0, "x1": nan(g1.shape)}, **kw)
+        f = last_block.convup_dgrad if ch == RU.OLD else dec2_block.convupn_dgrad          # (the planes of x0 say c0)
+        x1 = nan((B, L, ch[1] // 16, H, g1.shape[4], 16))
+        g = f(z["weight"].to(DEV), z["short"].to(DEV), g1, c16(z["gd"]), out={"x0": x0, "x1": x1}, **kw)
     else:
         assert cap == 0
         feat = c16(z["feat"])
@@ -98,8 +108,8 @@ def run(case, z, shape, cap=0):
     return out
 
 
-def device_truth(kind, z):
-    return P.truth(kind, {k: (None if v is None else v.to(DEV)) for k, v in z.items()})
+def device_truth(kind, z, ch=None):
+    return P.truth(kind, {k: (None if v is None else v.to(DEV)) for k, v in z.items()}, ch)
 
 
 def same_bytes(a, b):
@@ -123,10 +133,11 @@ def pairs(case):
 def test_wide_integers_are_bit_exact(case):
     kind = case[0]
     z = P.p1_inputs(case)
-    t = device_truth(kind, z)
-    grids = (0, pairs(case)) if kind in ("wgrad", "upwgrad") else (0,)
+    t = device_truth(kind, z, case[1])
+    # the weight gradients also at one share; the appended input gradients also at a prime grid of uneven shares
+    grids = (0, pairs(case)) if kind in ("wgrad", "upwgrad") else (0, R.PRIME_GRID) if P.is_new(case) else (0,)
     for cap in grids:
-        own = run(case, z, P.P1_SHAPE, cap)
+        own = run(case, z, P.p1_shape(case), cap)
         for name in P.OUTPUTS[kind]:
             want = t[name].to(torch.float32)
             assert torch.equal(want.to(torch.float64), t[name]) and (want != 0).any()
@@ -180,8 +191,10 @@ def test_one_chain_absorbs_at_most_its_own_positions(case, where):
 def test_everything_above_the_chain_is_f64(case, grid):
     kind, ch = case
     anchor, cap = (2.0 ** 32, 0) if grid == "default_grid" else (2.0 ** 36, pairs(case))
+    # share_positions knows the grids: at 512 -> 512 (256 pairs) the default grid is itself the one share of 104 tiles, so
+    # both parametrisations walk the same grid there, with their two anchors, and the chain is what bounds the positions
     positions = min(P.share_positions(kind, ch, P.P2_SHAPE, cap), chain_of(case))
-    assert positions == (chain_of(case) if cap else P.share_positions(kind, ch, P.P2_SHAPE, 0))
+    assert positions == (chain_of(case) if cap or pairs(case) == P.CAP else P.share_positions(kind, ch, P.P2_SHAPE, 0))
     t, got = p2(case, anchor, "up", cap)
     for name in P.PRODUCTS[kind]:
         err = np.abs(got[name] - t[name])
@@ -224,47 +237,48 @@ def col(e, dims_behind):
 @pytest.mark.parametrize("case", P.CASES, ids=ids(P.CASES))
 def test_a_power_of_two_per_channel_scales_every_output_exactly(case):
     kind, ch = case
-    z = P.normal_inputs(case, P.P3_SHAPE, P.P3_SEED)
-    plain = run(case, z, P.P3_SHAPE)
+    shape = P.p3_shape(case)
+    z = P.normal_inputs(case, shape, P.P3_SEED)
+    plain = run(case, z, shape)
     sc = lambda name, e, dim: P.scaled(z[name], e.cpu(), dim)
     if kind == "wgrad":
         a, b = ex(case, "x", ch[0]), ex(case, "upstream", ch[1])
-        own = run(case, dict(z, x=sc("x", a, 1), upstream=sc("upstream", b, 1)), P.P3_SHAPE)
+        own = run(case, dict(z, x=sc("x", a, 1), upstream=sc("upstream", b, 1)), shape)
         expect(case, "a, b", "weight", own["weight"], plain["weight"], col(b, 4) + col(a, 3))
         expect(case, "a, b", "shift", own["shift"], plain["shift"], b)
     elif kind == "upwgrad":
         c0, c1, cout = ch
         a, b1, bd = ex(case, "x", c0 + c1), ex(case, "g1", cout), ex(case, "gd", cout)
-        own = run(case, dict(z, x0=sc("x0", a[:c0], 1), x1=sc("x1", a[c0:], 1), g1=sc("g1", b1, 1), gd=sc("gd", bd, 1)), P.P3_SHAPE)
+        own = run(case, dict(z, x0=sc("x0", a[:c0], 1), x1=sc("x1", a[c0:], 1), g1=sc("g1", b1, 1), gd=sc("gd", bd, 1)), shape)
         expect(case, "a, b", "weight", own["weight"], plain["weight"], col(b1, 4) + col(a, 3))
         expect(case, "a, b", "short", own["short"], plain["short"], col(bd, 1) + a)
         expect(case, "a, b", "short_bias", own["short_bias"], plain["short_bias"], bd)
     elif kind == "dgrad":
         a, b = ex(case, "x", ch[0]), ex(case, "upstream", ch[1])
-        own = run(case, dict(z, upstream=sc("upstream", b, 1), weight=sc("weight", -b, 0)), P.P3_SHAPE)
+        own = run(case, dict(z, upstream=sc("upstream", b, 1), weight=sc("weight", -b, 0)), shape)
         expect(case, "b against 1 / b", "x", own["x"], plain["x"])                       # the products are the same numbers
         want_res = plain["res"] * P.pow2(col(b, 3))
         assert same_bytes(own["res"], want_res), (case, "res is a copy", mismatch(own["res"], want_res))
-        own = run(case, dict(z, weight=sc("weight", a, 1)), P.P3_SHAPE)
+        own = run(case, dict(z, weight=sc("weight", a, 1)), shape)
         expect(case, "a", "x", own["x"], plain["x"], col(a, 3))
         assert same_bytes(own["res"], plain["res"]), (case, "res is a copy")
     elif kind == "updgrad":
         c0, c1, cout = ch
         a, b1, bd = ex(case, "x", c0 + c1), ex(case, "g1", cout), ex(case, "gd", cout)
         own = run(case, dict(z, g1=sc("g1", b1, 1), weight=sc("weight", -b1, 0), gd=sc("gd", bd, 1), short=sc("short", -bd, 0)),
-                  P.P3_SHAPE)
+                  shape)
         for name in ("x0", "x1"):
             expect(case, "b against 1 / b", name, own[name], plain[name])
-        own = run(case, dict(z, weight=sc("weight", a, 1), short=sc("short", a, 1)), P.P3_SHAPE)
+        own = run(case, dict(z, weight=sc("weight", a, 1), short=sc("short", a, 1)), shape)
         expect(case, "a", "x0", own["x0"], plain["x0"], col(a[:c0], 3))
         expect(case, "a", "x1", own["x1"], plain["x1"], col(a[c0:], 3))
     else:
         a, b = ex(case, "feat", G.C), ex(case, "upstream", ch[0])
-        own = run(case, dict(z, feat=sc("feat", a, 1), upstream=sc("upstream", b, 1), weight=sc("weight", -b, 0)), P.P3_SHAPE)
+        own = run(case, dict(z, feat=sc("feat", a, 1), upstream=sc("upstream", b, 1), weight=sc("weight", -b, 0)), shape)
         expect(case, "a, b", "weight", own["weight"], plain["weight"], col(b, 1) + a)
         expect(case, "a, b", "bias", own["bias"], plain["bias"], b)
         expect(case, "b against 1 / b", "feat", own["feat"], plain["feat"])
-        own = run(case, dict(z, weight=sc("weight", a, 1)), P.P3_SHAPE)
+        own = run(case, dict(z, weight=sc("weight", a, 1)), shape)
         expect(case, "a", "feat", own["feat"], plain["feat"], col(a, 3))
 
 
@@ -290,8 +304,8 @@ def test_the_header_bounds_hold_below_the_normal_range(case, scales):
     z = {k: (v if k == "y" else half(v, e_up if k in P.ROLES[kind]["up"] else e_other)) for k, v in z.items()}
     if e_up == -130:
         assert all((z[k].abs() < 2.0 ** -126).all() and (z[k] != 0).float().mean() > 0.9 for k in P.ROLES[kind]["up"])
-    t = {k: v.cpu().numpy() for k, v in device_truth(kind, z).items()}
-    s = {k: v.cpu().numpy() for k, v in P.abs_truth(kind, {k: (None if v is None else v.to(DEV)) for k, v in z.items()}).items()}
+    t = {k: v.cpu().numpy() for k, v in device_truth(kind, z, ch).items()}
+    s = {k: v.cpu().numpy() for k, v in P.abs_truth(kind, {k: (None if v is None else v.to(DEV)) for k, v in z.items()}, ch).items()}
     got = {k: v.cpu().numpy() for k, v in run(case, z, P.P4_SHAPE).items()}
     n = int(np.prod(P.P4_SHAPE))
     label = f"probe 4 {P.case_id(case)} {scales}"
@@ -310,5 +324,6 @@ def test_the_header_bounds_hold_below_the_normal_range(case, scales):
         report(label, "x", err("x"), R.dgrad_bound(s["x"], ch[1]))
         assert np.array_equal(got["res"].view(np.int32), t["res"].astype(np.float32).view(np.int32)), (label, "res is a copy")
     else:
-        report(label, "x1", err("x1"), BD.dgrad_bound(s["x1"], hip.UPDGRAD_TERMS))
-        report(label, "x0", err("x0"), BD.dgrad_bound(s["x0"], hip.UPDGRAD_TERMS * P.n_terms_updgrad(P.P4_SHAPE)))
+        terms = hip.UPDGRAD_TERMS if ch == RU.OLD else hip.UPNDGRAD_TERMS(ch[2])
+        report(label, "x1", err("x1"), BD.dgrad_bound(s["x1"], terms))
+        report(label, "x0", err("x0"), BD.dgrad_bound(s["x0"], terms * P.n_terms_updgrad(P.P4_SHAPE)))

@@ -1,7 +1,11 @@
-"""CPU side of the probe tests of the eight gradient kernels (tests/test_gpu_grad_probes.py): the conditions on the data of
+"""CPU side of the probe tests of the eleven gradient kernels (tests/test_gpu_grad_probes.py): the conditions on the data of
 probes 1 and 3 that make their bit-exact assertions valid and sharp, the share arithmetic of probe 2 against the headers'
 host-side restatements, and a numpy model of hypothetical weight-gradient kernels (tests/grad_probe_ref.py: model_element)
 showing that the contract's kernel passes every assertion of probe 2 and that each faulty variant fails a named one.
+
+The appended cases (v2ce_convc_wgrad and v2ce_convc_dgrad at (128, 128), (512, 32), (32, 512), (512, 512), v2ce_convupn_dgrad
+at convupn_ref.TRIPLES) go through the same tests, and through those of their own slot tables, product widths and grids
+(16 and 256 pairs) below.  Their conditions are proved by convolving in f64 like the others', not by counting terms.
 
 The model describes kernels that do not exist; the GPU test never uses it as an expectation."""
 import functools
@@ -25,13 +29,13 @@ IDS = [P.case_id(c) for c in P.CASES]
 @functools.lru_cache(maxsize=None)
 def p1(case):
     z = P.p1_inputs(case)
-    return z, P.truth(case[0], z)
+    return z, P.truth(case[0], z, case[1])
 
 
 def changed_everywhere(case, z2, names, label, all_but=0.0):
     """Every non-zero element of the named outputs (all but the fraction `all_but`) differs between the truth and the truth of
     the altered inputs z2."""
-    t, t2 = p1(case)[1], P.truth(case[0], z2)
+    t, t2 = p1(case)[1], P.truth(case[0], z2, case[1])
     for name in names:
         live = t[name] != 0
         assert live.any(), (case, name)
@@ -45,7 +49,7 @@ def test_wide_integer_sums_are_exact_in_any_f32_order(case):
     channel of the upstream gradient is fed."""
     kind = case[0]
     z, t = p1(case)
-    a = P.abs_truth(kind, z)
+    a = P.abs_truth(kind, z, case[1])
     for name in P.OUTPUTS[kind]:
         assert float(a[name].max()) < 2 ** 24, (case, name, float(a[name].max()))
         assert torch.equal(t[name].to(torch.float32).to(torch.float64), t[name]), (case, name)
@@ -84,6 +88,15 @@ def test_a_precision_downgrade_changes_every_nonzero_output(case):
     z = p1(case)[0]
     names = P.PRODUCTS[kind]
     eleven = lambda v: P.round_to_bits(v, 11)
+    if kind == "updgrad" and P.is_new(case):
+        # no exception here: the four terms of a d_x0 element have one sign and lose in one direction (p1w_inputs), so every
+        # non-zero element changes; the 11-bit weights of the upsampled channels are rounded at 10 bits, the others at 11
+        ten = lambda v: P.round_to_bits(v, 10)
+        changed_everywhere(case, P.with_role(kind, z, "up", eleven), names, "up at 11 bits")
+        changed_everywhere(case, P.with_role(kind, z, "other", eleven), ("x1",), "other at 11 bits")
+        changed_everywhere(case, P.with_role(kind, z, "other", ten), ("x0",), "other at 10 bits")
+        changed_everywhere(case, P.with_role(kind, z, "both", P.drop_lowest_bit), names, "lo x lo dropped")
+        return
     if kind == "updgrad":
         changed_everywhere(case, P.with_role(kind, z, "up", eleven), ("x1",), "up at 11 bits")
         changed_everywhere(case, P.with_role(kind, z, "up", eleven), ("x0",), "up at 11 bits", all_but=0.01)
@@ -113,6 +126,91 @@ def test_wide_integer_positions_meet_the_first_tile_a_ragged_last_tile_and_a_fra
     assert all(min(np.diff(sorted(ws))) >= 4 for ws in by_batch.values())
 
 
+NEW = P.CASES[P.N_OLD:]
+NEW_IDS = [P.case_id(c) for c in NEW]
+
+
+def test_the_cases_were_appended():
+    """The seeds come from CASES.index: the first fifteen cases are where they were."""
+    assert P.N_OLD == 15 and IDS[:15] == [
+        "wgrad_32_32", "wgrad_64_64", "wgrad_64_32", "wgrad_32_64", "upwgrad_64_32_32", "upwgrad_128_64_64", "upwgrad_64_64_32",
+        "upwgrad_128_32_64", "dgrad_32_32", "dgrad_64_64", "dgrad_64_32", "dgrad_32_64", "updgrad_64_32_32", "head_20", "head_32"]
+    assert len(set(IDS)) == len(IDS) == 26
+    assert [c for c in NEW if c[0] == "wgrad"] == [c for c in P.WGRAD_CASES if P.is_new(c)] and all(c in P.CONV_CASES for c in NEW)
+
+
+@pytest.mark.parametrize("case", NEW, ids=NEW_IDS)
+def test_the_appended_products_have_22_or_23_significant_bits(case):
+    """Odd times odd is odd, so a product's significant bits are those of its magnitude: 2^22 <= |12 bits x 12 bits| < 2^23
+    (23 bits), 2^21 <= |12 bits x 11 bits| < 2^22 (22 bits: the weights of the upsampled channels of updgrad)."""
+    kind, ch = case
+    z = p1(case)[0]
+    span = lambda v: (float(v[v != 0].abs().min()), float(v.abs().max()))
+    up = [span(z[n]) for n in P.ROLES[kind]["up"]]
+    other = [span(z[n]) for n in P.ROLES[kind]["other"]]
+    if kind == "updgrad":
+        c0 = ch[0]
+        lo, hi = span(z["weight"][:, :c0])
+        assert 2 ** 10 < lo and hi < 2 ** 11 and (z["weight"][:, :c0].abs() % 4 == 1).all()
+        assert (z["weight"][:, :c0].sign() == z["weight"][:, :c0, :1, :1, :1].sign()).all()       # one sign per (co, ci)
+        assert 2 ** 21 <= lo * min(u[0] for u in up) and hi * max(u[1] for u in up) < 2 ** 22
+        other = [span(z["weight"][:, c0:]), span(z["short"])]
+    assert 2 ** 22 <= min(u[0] for u in up) * min(o[0] for o in other)
+    assert max(u[1] for u in up) * max(o[1] for o in other) < 2 ** 23
+
+
+def test_the_appended_slot_tables_hold_disjoint_neighbourhoods_and_ragged_tiles():
+    B, L, H, W = P.P1W_SHAPE
+    assert G.conv_tiles(*P.P1W_SHAPE) == 72
+    assert G.tile_of(P.P1W_SHAPE, 71) == (1, 3, 4, 5, 128, 131)         # the last tile: one row, three columns
+    for kind, n in (("wgrad", 1760), ("dgrad", 352), ("updgrad", 264)):
+        slots = P.p1w_slots(kind)
+        assert len(set(slots)) == len(slots) == n and all(b < B and l < L and h < H and w < W for b, l, h, w in slots)
+        assert slots[0] == (0, 0, 0, 0) and slots[-1][:2] == (1, 3) and slots[-1][3] >= 128
+    assert P.p1w_slots("wgrad")[-1] == (1, 3, 4, 129)
+    # the largest and the smallest slot number within a tap of every position (0 and n + 1 where there is none)
+    F = torch.nn.functional
+    for kind in ("dgrad", "updgrad"):
+        slots = P.p1w_slots(kind)
+        ids = torch.zeros((B, 1, L, H, W))
+        for i, (b, l, h, w) in enumerate(slots):
+            ids[b, 0, l, h, w] = i + 1
+        most = F.max_pool3d(ids, 3, 1, 1)
+        least = -F.max_pool3d(-torch.where(ids > 0, ids, torch.full_like(ids, len(slots) + 1.0)), 3, 1, 1)
+        if kind == "updgrad":                                          # ... of every 2 x 2 pool of output positions
+            most, least = F.max_pool3d(most, (1, 2, 2), ceil_mode=True), -F.max_pool3d(-least, (1, 2, 2), ceil_mode=True)
+        assert ((most == 0) | (most == least)).all() and (most > 0).any(), kind
+    ids = torch.zeros((B, 1, L, H, W))                                 # (and the check can fail: every third column under the pool)
+    for i, (b, l, h, w) in enumerate(P.p1w_slots("dgrad")):
+        ids[b, 0, l, h, w] = i + 1
+    most = F.max_pool3d(F.max_pool3d(ids, 3, 1, 1), (1, 2, 2), ceil_mode=True)
+    least = -F.max_pool3d(F.max_pool3d(-torch.where(ids > 0, ids, torch.full_like(ids, 353.0)), 3, 1, 1), (1, 2, 2), ceil_mode=True)
+    assert ((most > 0) & (most != least)).any()
+    for kind, n in (("wgrad", 32), ("wgrad", 128), ("wgrad", 512), ("dgrad", 16), ("dgrad", 64), ("dgrad", 256),
+                    ("updgrad", 64), ("updgrad", 128)):
+        at, later = P.p1w_pick(kind, n)
+        assert len(set(at)) == n and at[0] == (0, 0, 0, 0) and at[-1] == P.p1w_slots(kind)[-1]
+        assert max(w for _, _, _, w in at[:n // 2]) + 1 < later - 1 and min(w for _, _, _, w in at[n // 2:]) == later
+
+
+@pytest.mark.parametrize("case", [c for c in NEW if c[0] == "updgrad"], ids=[P.case_id(c) for c in NEW if c[0] == "updgrad"])
+def test_the_truth_of_the_appended_upsample_cases_is_the_numpy_restatement(case):
+    """grad_probe_ref.updgrad_truth against convupn_dgrad_ref.dgrad (which torch's f64 autograd validates), and at
+    (64, 32, 32) against grad_walk_ref.convup_dgrad."""
+    from tests import convupn_dgrad_ref as RD
+    c0, c1, cout = case[1]
+    z = RD.inputs((2, 3, 5, 7), c0, c1, cout)
+    want = RD.truth((2, 3, 5, 7), c0, c1, cout)
+    got = P.updgrad_truth(c0, *(torch.from_numpy(z[k].copy()) for k in ("kw", "ks", "g1", "gd")))
+    for k in ("d_x0", "d_x1", "abs_x0", "abs_x1"):
+        assert got[k].shape == want[k].shape
+        assert np.allclose(got[k].numpy(), want[k], rtol=1e-12, atol=1e-12), k
+    zo = RD.inputs((2, 3, 5, 7), *RU.OLD)
+    args = [torch.from_numpy(zo[k].copy()) for k in ("kw", "ks", "g1", "gd")]
+    old, mine = G.convup_dgrad(*args), P.updgrad_truth(64, *args)
+    assert all(torch.equal(old[k], mine[k]) for k in mine)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # probe 2
 
@@ -139,7 +237,10 @@ def test_share_arithmetic_is_the_headers(case):
     assert P.wgrad_shares(kind, ch, TILES2, pairs) == 1 and P.share_positions(kind, ch, P.P2_SHAPE, pairs) == N2
     sizes = G.share_sizes(TILES2, P.wgrad_shares(kind, ch, TILES2))
     assert sum(sizes) == TILES2 and P.share_positions(kind, ch, P.P2_SHAPE, 0) == sizes[0] * 128
-    assert sizes[0] * 128 <= hip.WGRAD_CHAIN
+    if pairs == P.CAP:                                                 # 512 -> 512: the default grid is the one share
+        assert sizes == [TILES2] and kind == "wgrad" and ch == (512, 512)
+    else:
+        assert sizes[0] * 128 <= hip.WGRAD_CHAIN
 
 
 def test_the_walk_of_probe_2_is_three_whole_chains_and_eight_tiles():
@@ -159,23 +260,23 @@ ONE_SHARE = [(0, N2)]
 DEFAULT_GRID = P.boundaries(G.share_sizes(TILES2, min(TILES2, 256)))        # v2ce_conv32_wgrad: one tile a share
 
 
-def passes(assertion, **kernel):
-    """Does the modelled kernel pass the named assertion of probe 2?"""
+def passes(assertion, grid=DEFAULT_GRID, **kernel):
+    """Does the modelled kernel pass the named assertion of probe 2?  grid: the shares of the default grid."""
     if assertion == "a: header bound, one share, anchor 2^24":
         p = centre_products(2.0 ** 24)
         got = P.model_element(p, ONE_SHARE, **kernel)
         return abs(float(got) - p.sum()) <= float(P.header_bound(p.sum(), p.sum(), N2, hip.WGRAD_CHAIN))
     if assertion == "b: share bound, default grid, anchor 2^32":
         p = centre_products(2.0 ** 32)
-        got = P.model_element(p, DEFAULT_GRID, **kernel)
-        return abs(float(got) - p.sum()) <= float(P.share_bound(p.sum(), 128))
+        got = P.model_element(p, grid, **kernel)
+        return abs(float(got) - p.sum()) <= float(P.share_bound(p.sum(), min(grid[0][1], hip.WGRAD_CHAIN)))
     if assertion == "b: share bound, one share, anchor 2^36":
         p = centre_products(2.0 ** 36)
         got = P.model_element(p, ONE_SHARE, **kernel)
         return abs(float(got) - p.sum()) <= float(P.share_bound(p.sum(), hip.WGRAD_CHAIN))
     assert assertion == "c: f64-throughout outputs are the exact sum rounded once"
     ok = True
-    for anchor, shares in ((2.0 ** 24, ONE_SHARE), (2.0 ** 32, DEFAULT_GRID), (2.0 ** 36, ONE_SHARE)):
+    for anchor, shares in ((2.0 ** 24, ONE_SHARE), (2.0 ** 32, grid), (2.0 ** 36, ONE_SHARE)):
         p = centre_products(anchor)
         ok = ok and P.is_round32(P.model_element(p, shares, **kernel), p.sum())
     return ok
@@ -206,6 +307,39 @@ def test_the_contract_kernel_passes_every_assertion_of_probe_2():
 def test_each_faulty_kernel_fails_the_assertion_named_for_it(fault):
     kernel, caught_by = FAULTS[fault]
     assert not passes(caught_by, **kernel), (fault, caught_by)
+
+
+# the default grids of the appended weight-gradient cases: 16 pairs (128 -> 128, 512 -> 32, 32 -> 512) give 16 shares of 6 or 7
+# tiles, 256 pairs (512 -> 512) the one share
+WIDE_GRIDS = {p: P.boundaries(G.share_sizes(TILES2, min(TILES2, P.CAP // p))) for p in (16, 256)}
+
+
+def test_the_grids_of_the_appended_cases_are_the_modelled_ones():
+    want = {P.pairs_of(*c) for c in P.WGRAD_CASES if P.is_new(c)}
+    assert want == set(WIDE_GRIDS) and len(WIDE_GRIDS[16]) == 16 and WIDE_GRIDS[256] == ONE_SHARE
+    for c in (c for c in P.WGRAD_CASES if P.is_new(c)):
+        assert WIDE_GRIDS[P.pairs_of(*c)][0][1] == P.share_positions(*c, P.P2_SHAPE, 0)
+
+
+@pytest.mark.parametrize("pairs", WIDE_GRIDS)
+def test_at_the_appended_pair_counts_each_fault_breaks_an_assertion(pairs):
+    """A 64-tile chain breaks (a) and an f32 partial slot breaks (b) at one share, whatever the pair count.  An f32 finish
+    breaks (b) at the default grid of 16 pairs; at 256 pairs the default grid is one share, the finish adds one slot to
+    zero, and an f32 finish is the contract's kernel byte for byte: there is nothing to catch."""
+    grid = WIDE_GRIDS[pairs]
+    for a in ASSERTIONS:
+        assert passes(a, grid, **CONTRACT), a
+    assert not passes(ASSERTIONS[0], grid, **dict(CONTRACT, chain=64 * 128))
+    assert not passes(ASSERTIONS[2], grid, **dict(CONTRACT, partial=np.float32))
+    f32_finish = dict(CONTRACT, finish=np.float32)
+    if pairs == 256:
+        for anchor in (2.0 ** 24, 2.0 ** 32, 2.0 ** 36):
+            p = centre_products(anchor)
+            assert P.model_element(p, grid, **f32_finish) == P.model_element(p, grid, **CONTRACT)
+        # the chain is what the default grid's anchor of 2^32 sees there: a 64-tile chain breaks (b) as well
+        assert not passes(ASSERTIONS[1], grid, **dict(CONTRACT, chain=64 * 128))
+    else:
+        assert not passes(ASSERTIONS[1], grid, **f32_finish)
 
 
 def test_an_f32_accumulator_fails_the_exactness_of_the_f64_throughout_outputs():
@@ -243,7 +377,7 @@ def test_scaled_normals_stay_inside_the_normal_range(case):
     """No |value|, no |product of paired values| and no |truth| of the plain data lies outside [2^-60, 2^40]; with exponents
     of at most 16 on both operands nothing then leaves f32's normal range, and the scaling commutes with every rounding."""
     kind = case[0]
-    z = P.normal_inputs(case, P.P3_SHAPE, P.P3_SEED)
+    z = P.normal_inputs(case, P.p3_shape(case), P.P3_SEED)
     lo, hi = P.P3_RANGE
     span = {}
     for role in ("up", "other"):
@@ -251,7 +385,7 @@ def test_scaled_normals_stay_inside_the_normal_range(case):
         span[role] = (float(a.min()), float(a.max()))
         assert lo <= span[role][0] and span[role][1] <= hi, (case, role, span[role])
     assert lo <= span["up"][0] * span["other"][0] and span["up"][1] * span["other"][1] <= hi, (case, span)
-    t = P.truth(kind, z)
+    t = P.truth(kind, z, case[1])
     for name in P.OUTPUTS[kind]:
         a = t[name].abs()
         a = a[a != 0] if name == "res" else a                          # d_res is a copy: the mask's zeros are zeros
